@@ -225,6 +225,43 @@ def other_configs(args, local, torch, config, env, skip):
     return out
 
 
+DUMP_BYTES = 32 << 20  # per-arena arrays of --dump-outputs; past this, a fixed seeded sample of the arenas
+DUMP_STATE_ARENAS = 8  # arenas whose whole state (sf_dump_arena) is written
+
+
+def dump_outputs(directory, g, cfg, suffix=""):
+    """--dump-outputs: what the timed path (sf_step_device) computed, read back after its last step through the calls a
+    caller of it makes: per arena the state digest, the done flag, the commanded agents' alive flags and end-of-episode
+    result records; and the whole state of DUMP_STATE_ARENAS arenas.  The arenas are all of them, or a sample drawn with
+    a fixed seed when the arrays would exceed DUMP_BYTES (arena_index.npy names them).  Integers are written as
+    float64, exactly: the 64-bit digest as its high and low 32-bit halves, records of the state as their int32 words."""
+    os.makedirs(directory, exist_ok=True)
+    A, n = cfg.arenas, cfg.n_agents
+    per_arena = 8 * (1 + 2 + 1 + n + 8 * n)
+    rng = np.random.default_rng(20240601)
+    idx = np.arange(A) if A * per_arena <= DUMP_BYTES else np.sort(rng.choice(A, DUMP_BYTES // per_arena, replace=False))
+    dig = g.digest()[idx]
+    out = {"arena_index": idx.astype(np.float64),
+           "digest": np.stack([dig >> np.uint64(32), dig & np.uint64(0xFFFFFFFF)], axis=1).astype(np.float64),
+           "done": g.done()[idx].astype(np.float64),
+           "agent_alive": g.agent_alive()[idx].astype(np.float64),
+           "results": g.results()[idx].astype(np.float64)}
+    sidx = np.sort(rng.choice(A, min(A, DUMP_STATE_ARENAS), replace=False))
+    words = lambda rec: np.frombuffer(bytes(rec), dtype=np.int32).astype(np.float64)
+    parts = {k: [] for k in ("hdr", "humans", "zombies", "bullets", "portals", "flags", "dmg", "pidx")}
+    for a in sidx:
+        hdr, hs, zs, bs, ps, flags, dmg, pidx = g.dump_raw(int(a))
+        parts["hdr"].append(words(hdr))
+        for k, recs in (("humans", hs), ("zombies", zs), ("bullets", bs), ("portals", ps)):
+            parts[k].append(np.stack([words(r) for r in recs]))
+        for k, v in (("flags", flags), ("dmg", dmg), ("pidx", pidx)):
+            parts[k].append(v.astype(np.float64))
+    out["state_arena_index"] = sidx.astype(np.float64)
+    out.update({"state_" + k: np.stack(v) for k, v in parts.items()})
+    for k, v in out.items():
+        np.save(os.path.join(directory, k + suffix + ".npy"), v)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a torch.distributed environment: start the N ranks as a child process
     (nothing in this process has touched a GPU) and pass its output and exit code through."""
@@ -253,6 +290,8 @@ def main():
     ap.add_argument("--no-policy", action="store_true", help="skip the closed loop with the on-device policy network")
     ap.add_argument("--no-other-configs", action="store_true", help="skip the other BASELINE configurations")
     ap.add_argument("--preroll", type=int, default=PREROLL, help="untimed steady-state steps before --warmup")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed steps computed, as of their last step, to DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -295,12 +334,7 @@ def main():
     g.reset(tb, sr)
 
     pre = args.preroll
-    # a timed region shorter than ~50 ms (the driver's --steps 20 is one 0.4 ms launch) is one sample of one launch:
-    # it is then repeated REPEATS times on fresh command windows, each repeat bracketed like the first, and the line
-    # reports the median (min / max beside it).  Every repeat times EXACTLY --steps steps.
-    REPEATS, SHORT_S = 21, 0.05
-    # the repeats' command windows are generated (and uploaded) only if the first timed region turns out short: the
-    # default --steps 1000 never repeats, and 21 windows of it would be 88 MB per agent for nothing
+    # the timed region is exactly --steps steps, once: ms_per_step is its time / --steps
     total = pre + args.warmup + args.steps
     cmds, _ = config.bench_commands(args.arenas, cfg.n_agents, total, seed0=shard.command_seed(w, rank))
     d_cmds = torch.from_numpy(cmds).cuda()  # resident in HBM before the timed region
@@ -380,16 +414,10 @@ def main():
             t = float(tt.item())
         return t
 
-    dts = [timed(pre + args.warmup)]
-    if dts[0] < SHORT_S:  # (the same decision on every rank: dts[0] is the maximum over ranks)
-        total = pre + args.warmup + args.steps * REPEATS
-        cmds, _ = config.bench_commands(args.arenas, cfg.n_agents, total, seed0=shard.command_seed(w, rank))  # (same stream, longer)
-        d_cmds = torch.from_numpy(cmds).cuda()
-        torch.cuda.synchronize()
-        for r_ in range(1, REPEATS):
-            dts.append(timed(pre + args.warmup + r_ * args.steps))
-    dt = float(np.median(dts))
+    dt = timed(pre + args.warmup)
     k_ms, k_launches = g.kernel_time(False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, g, cfg, "" if world == 1 else "_rank%d" % rank)
     rccl_ranks = None
     if rccl:
         try:
@@ -454,7 +482,7 @@ def main():
         # of their games first.
         halves = []
         if args.arenas % 2 == 0:
-            done_steps = pre + args.warmup + args.steps * len(dts)
+            done_steps = pre + args.warmup + args.steps
             for j in range(2):
                 n = args.arenas // 2
                 wj = config.baseline_workload(args.workload, arenas=n, device=local)
@@ -609,7 +637,7 @@ def main():
         env_steps = world * args.arenas * args.steps
         bytes_step = algorithmic_bytes_per_step(cfg)
         avg_launch_s = (k_ms / 1e3) / max(1, k_launches)
-        steps_per_launch = args.steps * len(dts) / max(1, k_launches)
+        steps_per_launch = args.steps / max(1, k_launches)
         achieved = bytes_step * args.arenas * steps_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
         kpl_actual = int(round(steps_per_launch))
         traffic = pmc_traffic(args.workload, args.arenas, kpl_actual) if abs(steps_per_launch - kpl_actual) < 1e-9 else None
@@ -621,9 +649,6 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": dt * 1e3 / args.steps,
-            "repeats": {"n": len(dts), "min_ms_per_step": min(dts) * 1e3 / args.steps, "max_ms_per_step": max(dts) * 1e3 / args.steps,
-                        "what": "the timed region of exactly --steps steps, repeated on fresh command windows when it is "
-                                "shorter than %d ms; value / ms_per_step are the median" % int(SHORT_S * 1e3)},
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

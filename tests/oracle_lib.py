@@ -16,9 +16,8 @@ def lib():
     if _LIB is None:
         path = os.path.join(ROOT, "oracle", "libsf_oracle.so")
         src = os.path.join(ROOT, "oracle", "sf_oracle.c")
-        if not os.path.exists(path) or (os.path.getmtime(path) < os.path.getmtime(src) and os.path.isdir("/root/reference")):
-            # (re)built only in the build container, or when missing altogether: the GPU box uses the file that
-            # __graft_entry__.build() made, which travels with the snapshot
+        if not os.path.exists(path) or os.path.getmtime(path) < os.path.getmtime(src):
+            # missing, or older than its source: __graft_entry__.build() normally leaves it up to date
             subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "libsf_oracle.so"])
         L = C.CDLL(path)
         L.sfo_create.argtypes = [C.POINTER(abi.Config)]

@@ -1,7 +1,10 @@
 """Driver for oracle/_ref/sf_ref_tick: the reference's own tick path compiled head-less (oracle/ref_tick.py: the
 client's headers with only the SFML / keyboard / menu member functions blanked, every other line unedited).
-Test infrastructure only.  available() is False where the binary was never built or the reference's data files
-(Items/, character/) are not on this machine."""
+Test infrastructure only.  available() is False where the binary was never built.  The data files a game reads
+(Items/*.txt, character/*.txt) are written for every run from the committed tables: tests/golden/kat.json's "items"
+(what the reference's download_items() read from its Items/, tests/test_ref_slices.py) and config.HUMAN_TOKENS /
+HUMAN_ENEMY_TOKENS (character/human.txt, human_enemy.txt); the item names, which only label the menus, are placeholders."""
+import json
 import os
 import shutil
 import subprocess
@@ -13,7 +16,7 @@ from strikeforce_amd import abi, config
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "oracle", "_ref", "sf_ref_tick")
-REF_CLIENT = "/root/reference/StrikeForce-client"
+ITEMS = os.path.join(ROOT, "tests", "golden", "kat.json")
 MODES = {abi.MODE_SOLO: "Solo", abi.MODE_TIMER: "Timer", abi.MODE_SQUAD: "Squad", abi.MODE_BATTLE: "Battle_Royal"}
 
 
@@ -21,19 +24,32 @@ NATIVE = (3, 30, 100, 9000, 9000, 9000, 9000)  # gameplay.hpp:37
 
 
 def available():
-    return os.path.exists(BIN) and os.path.isdir(os.path.join(REF_CLIENT, "Items"))
+    return os.path.exists(BIN)
 
 
 def binary(dims, squad_agents=False):
-    """The build for these dimensions: the native one as __graft_entry__.build() left it; a patched-dimensions one
-    (gameplay.hpp:37 replaced, oracle/ref_tick.py) is compiled on first use where the checkout exists."""
+    """The build for these dimensions as __graft_entry__.build() left it (oracle/ref_tick.py: the native one, and one per
+    patched dimensions line in its TEST_DIMS), or None."""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "oracle"))
     import ref_tick
     path = ref_tick.binary_for(dims, squad_agents)
-    if path != BIN and os.path.isdir(REF_CLIENT):
-        ref_tick.build(quiet=True, dims=dims, squad_agents=squad_agents)
     return path if os.path.exists(path) else None
+
+
+def write_data_files(directory):
+    """Items/cons0-3.txt, throw0-3.txt, w0-7.txt (Item.hpp:69-74,113-118,149-154: name, then one number per line) and
+    character/human.txt, human_enemy.txt (Character.hpp:650-709: 32 numbers, one per line) under `directory`."""
+    items = json.load(open(ITEMS))["items"]
+    os.makedirs(os.path.join(directory, "Items"))
+    for kind, prefix in (("cons", "cons"), ("throw", "throw"), ("weapon", "w")):
+        for i, row in enumerate(items[kind]):
+            with open(os.path.join(directory, "Items", "%s%d.txt" % (prefix, i)), "w") as fh:
+                fh.write("%s%d\n" % (prefix, i) + "".join("%d\n" % v for v in row))
+    os.makedirs(os.path.join(directory, "character"))
+    for name, tokens in (("human", config.HUMAN_TOKENS), ("human_enemy", config.HUMAN_ENEMY_TOKENS)):
+        with open(os.path.join(directory, "character", name + ".txt"), "w") as fh:
+            fh.write("\n".join(str(int(t)) for t in tokens))
 
 
 class RefTick:
@@ -56,8 +72,7 @@ class RefTick:
         self.cfg = cfg
         self.dir = tempfile.mkdtemp(prefix="sf_reftick_run_")
         os.makedirs(os.path.join(self.dir, "map"))
-        for d in ("Items", "character"):
-            os.symlink(os.path.join(REF_CLIENT, d), os.path.join(self.dir, d))
+        write_data_files(self.dir)
         cells = cfg.rows * cfg.cols
         chars = bytes(workload._map.raw).decode("ascii")
         portal = list(workload._portal)

@@ -31,8 +31,7 @@ def build(tmp_path, lib_dir, lib_name):
 
 def emu_lib():
     d = os.path.join(ROOT, "tests", "emu")
-    if os.path.isdir("/root/reference") or not os.path.exists(os.path.join(d, "libsf_emu_abi.so")):
-        subprocess.check_call(["make", "-s", "-C", d, "libsf_emu_abi.so"])
+    subprocess.check_call(["make", "-s", "-C", d, "libsf_emu_abi.so"])  # (a no-op when it is up to date)
     return d, "sf_emu_abi"
 
 

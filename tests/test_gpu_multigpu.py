@@ -52,4 +52,6 @@ def test_bench_starts_its_own_ranks():
     assert d["value"] > 0 and d["scaling"] == "weak"
     assert "configs[2]" in d["config"]["workload"]
     assert "rccl_ranks" in d and d["rccl_ranks"] is None  # (gloo rehearsal: no RCCL communicator; a real run reports N)
-    assert d["repeats"]["n"] == 21                         # a 20-step region is short: median of 21 repeats
+    # the timed region is exactly --steps steps (one 20-step launch), and ms_per_step is its time per step
+    assert d["roofline"]["launches"] == 1 and d["config"]["steps_per_launch"] == 20
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 2 * 512) < 1e-6 * 2 * 512

@@ -123,7 +123,10 @@ def _check(results, worlds, out, teams):
 
 def test_three_clients_through_the_reference_server():
     teams = [1, 2, 1]
-    results, worlds, out = run_match(Oracle, teams, quit_at=(1, 60), ticks=250)
+    # the seed is the server's clock: the player who quits at iteration 60 gets the 15000-Hp record (RECORDS[1]) so that
+    # no seed lets it die first
+    results, worlds, out = run_match(Oracle, teams, quit_at=(1, 60), ticks=250,
+                                     records=[config.HUMAN_ENEMY_TOKENS, RECORDS[1], config.HUMAN_ENEMY_TOKENS])
     _check(results, worlds, out, teams)
     assert [r[5] for r in sorted(results)][1] == "quit"
     assert "quited" in out  # the server's own log line for the '_' it relayed (server.cpp:88-89)

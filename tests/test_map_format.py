@@ -40,19 +40,18 @@ def test_three_floor_directory_round_trip_and_parity(tmp_path):
     assert {h.f for h in d.humans if h.alive} >= {0, 2}  # Squad: team-mates on floor 0, opponents on floor 2
 
 
-REF_MAP_DIR = "/root/reference/StrikeForce-client/map"
+FIXTURE_MAP_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "maps")
+# SHA-256 of the reference checkout's map/floor1-3.txt, the files the fixtures were copied from
+REF_MAP_SHA256 = {1: "7c2f684d4d89c1b3dc79f67d5883f529bb2ef65a3dd32564f58a87f8755f2c02",
+                  2: "f2be8c8d1f9989475048069bf30de5e47075f7391c7006ada9401a63339660b8",
+                  3: "42925bb7f8c8300f8e4854c2516f289278d68f87b6fa12b93271b85b32f44615"}
 
 
 def test_native_world_on_the_reference_maps_when_present():
     """The shipped 3 x 30 x 100 world (map/floor1-3.txt: 6 exits, '^'/'v' entrances in the top border rows) with the
-    reference's level-10 account, Solo and Squad.  Reads the reference checkout, so it only runs where that exists
-    (never on the GPU box); the data is not copied."""
-    import os
-    import pytest
+    reference's level-10 account, Solo and Squad, read from the committed copies of those files."""
     import fuzz_cases
-    if not os.path.isdir(REF_MAP_DIR):
-        pytest.skip("no reference checkout")
-    m, p = config.load_reference_maps(REF_MAP_DIR)
+    m, p = config.load_reference_maps(FIXTURE_MAP_DIR)
     assert len(m) == 9000 and m.count(b"O") == 6
     for mode, agents in ((abi.MODE_SOLO, 1), (abi.MODE_SQUAD, 3)):
         cfg = config.make_config(2, 30, 100, floors=3, H=64, Z=64, B=256, P=32, mode=mode, level=4, n_agents=agents,
@@ -67,16 +66,12 @@ def test_native_world_on_the_reference_maps_when_present():
         assert (o.results() == e.results()).all()
 
 
-FIXTURE_MAP_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "maps")
-
-
 def test_committed_map_fixtures_equal_the_checkout():
-    """tests/golden/maps/floor1-3.txt are the reference's map data, byte for byte."""
-    if not os.path.isdir(REF_MAP_DIR):
-        pytest.skip("no reference checkout")
+    """tests/golden/maps/floor1-3.txt are the reference's map data, byte for byte (their digests are the checkout's)."""
+    import hashlib
     for k in (1, 2, 3):
-        assert open(os.path.join(FIXTURE_MAP_DIR, "floor%d.txt" % k), "rb").read() == \
-            open(os.path.join(REF_MAP_DIR, "floor%d.txt" % k), "rb").read()
+        data = open(os.path.join(FIXTURE_MAP_DIR, "floor%d.txt" % k), "rb").read()
+        assert hashlib.sha256(data).hexdigest() == REF_MAP_SHA256[k], k
 
 
 def _native_world(impl_a, impl_b, steps):
