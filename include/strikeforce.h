@@ -235,9 +235,44 @@ int sf_observe_sparse_device(sf_env *env, uint32_t *d_keys, float *d_vals, uint3
 int sf_observe_overflow_device(sf_env *env, const uint32_t *d_counts, int32_t cap, float *d_dense, float *d_pov);
 
 /* Per (arena, agent) 8 x int32: kills, teams_kills, loot, damage, effect, Hp, frames, outcome
- * (gameplay.hpp:461,588-593,625-629; Character.hpp:294).  Latched at episode end. */
+ * (gameplay.hpp:461,588-593,625-629; Character.hpp:294).  Latched at episode end: one record per arena, which the next
+ * end overwrites.  To receive every finished episode's record, also those of an arena that ended two inside one
+ * launch, turn on the episode log below. */
 int sf_results(sf_env *env, int32_t *out_host);
 int sf_results_device(sf_env *env, int32_t *d_out);
+
+/* ---- episode log: every finished episode's result record, kept on the device ---------------------------------
+ * The reference ends a game where `if(check_end()) break;` leaves play()'s loop (gameplay.hpp:1450; check_end
+ * gameplay.hpp:1102-1229) and the caller reads the counters of that game (the fields sf_results carries,
+ * gameplay.hpp:461,588-593,625-629; Character.hpp:294).  With the log on, each arena keeps a device ring of its last
+ * `depth` finished episodes, written by the step kernels at the moment check_end ends a game, whichever entry point
+ * stepped it (sf_step, sf_step_device, sf_step_begin / sf_step_end).  A game that sf_reset's own first loop top ends is
+ * not counted by sf_arena_hdr.episodes (the arena stands still before its first iteration) and is not logged.  Off by
+ * default; while off nothing is allocated, the step kernels launched are the ones without log code, and nothing behaves
+ * differently.
+ * One record = SF_EPISODE_HDR_WORDS header words, then n_agents x 8 words:
+ *   arena, episode, tb_lo, tb_hi, serial_lo, serial_hi, steps, outcome | per agent exactly what sf_results held then
+ * episode: 0-based ordinal since sf_reset (sf_arena_hdr.episodes while it ran); tb / serial: the seed of the episode
+ * that ended (with auto_reset and reseed_stride, tb = the arena's first tb + episode x stride: a key unique across
+ * shards); steps: loop iterations, as sf_arena_hdr.steps; outcome: SF_WON ... as in sf_results. */
+#define SF_EPISODE_HDR_WORDS 8
+/* depth: a power of two in [1, 64] (re)allocates an empty ring; 0 turns the log off and frees it.  Not between
+ * sf_step_begin and sf_step_end.  Only episodes that end from now on are offered (each arena's cursor starts at its
+ * current count); sf_reset empties the rings and restarts the cursors at episode 0. */
+int sf_episode_log(sf_env *env, int32_t depth);
+/* The records not delivered yet, as one dense list in arena-ascending then episode-ascending order, at most max_records
+ * of them: d_out [max_records][SF_EPISODE_HDR_WORDS + 8 n_agents] int32 and d_counts [3] = written, lost (ended since
+ * the last call but already overwritten in the ring: more than `depth` in between), still pending (did not fit; offered
+ * again by the next call).  Each arena's cursor advances past what it delivered and what it lost.  The device form is
+ * two kernel launches on the library's stream with no host synchronisation: it may be captured in a graph behind
+ * sf_step_device.  A captured graph holds the ring's, the cursors' and the plan's addresses and the k_step instance
+ * chosen at capture time (the log has one of its own): any later sf_episode_log call invalidates it, so capture again
+ * after one.  SF_ERR_STATE while the log is off or between sf_step_begin and sf_step_end. */
+int sf_episodes(sf_env *env, int32_t *out_host, int32_t max_records, int32_t *counts_host);
+int sf_episodes_device(sf_env *env, int32_t *d_out, int32_t max_records, int32_t *d_counts);
+/* The raw rings, out [arenas][depth][record] int32 (episode e of an arena in slot e & (depth - 1)); empty slots have
+ * episode == -1.  Leaves the cursors alone. */
+int sf_episode_ring(sf_env *env, int32_t *out_host);
 
 /* ---- multi-GPU: the one exchange step ------------------------------------------
  * Arenas are sharded over one sf_env per GPU with no data-path collective.  The result records of all shards are
@@ -255,6 +290,10 @@ int sf_comm_ranks(sf_env *env, int32_t *ranks);
  * ([world][arenas][n_agents][8] int32, device memory) on a side stream owned by the library: the call returns at
  * once and the gather runs beside the launches that follow.  d_out is complete after sf_comm_wait. */
 int sf_results_allgather(sf_env *env, int32_t *d_out);
+/* The same for the episode log: snapshot the raw rings (sf_episode_ring's layout) and all-gather them into d_out
+ * ([world][arenas][depth][record] int32, device memory) on the side stream; staging is allocated on first use.  The
+ * cursors are not touched: a consumer keeps its own per (rank, arena) and takes the records whose episode is newer. */
+int sf_episodes_allgather(sf_env *env, int32_t *d_out);
 /* Make the env's stream (and, with host_too != 0, the calling thread) wait for every gather issued so far. */
 int sf_comm_wait(sf_env *env, int32_t host_too);
 
@@ -262,7 +301,8 @@ int sf_comm_wait(sf_env *env, int32_t host_too);
  * episode has ended (the arena then stands still).  With auto_reset: the number of episodes (saturating at 255) that
  * ended during the LAST sf_step / sf_step_device call, over all of its k iterations; the arena has already restarted.
  * The result record (sf_results) is the one of the last episode that ended; a caller that gathers records after
- * multi-step launches tells fresh from stale ones by this count or by sf_arena_hdr.episodes. */
+ * multi-step launches tells fresh from stale ones by this count or by sf_arena_hdr.episodes, and the episode log
+ * (sf_episode_log, sf_episodes_device) hands over every ended episode's record, not only the last. */
 int sf_done(sf_env *env, uint8_t *out_host);
 /* The same flag on the device, one byte per (arena, agent) (every agent of an arena gets its arena's flag), in the
  * layout the policy library's reset_memory entry (strikeforce_policy.h) takes: with auto_reset it marks the agents whose game just restarted, i.e. where the

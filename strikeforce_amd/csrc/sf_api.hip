@@ -39,14 +39,16 @@ __global__ __launch_bounds__(64) void k_reset(Params p, const uint64_t *tb, cons
   Core<WaveGfx950, NB, HP, BM, ZL>::reset_body(lds, p, (int)blockIdx.x, tb, serial);
 }
 
-template <int NB, bool HP, bool BM, bool ZL>
+// LOG: the instance launched while the episode log is on (sf_core.hpp latch_results<LOG>); with the log off the kernel is
+// the one without log code
+template <int NB, bool HP, bool BM, bool ZL, bool LOG>
 __global__ __launch_bounds__(64) void k_step(Params p, const uint8_t *cmds, int k) {
   extern __shared__ __attribute__((aligned(2048))) uint8_t lds[];  // the RNG power table comes first (W::pow_pair)
   const int a = p.perm ? (int)gptr(p.perm)[blockIdx.x] : (int)blockIdx.x;
 #ifdef SF_DIAG_STAMPS
   if (threadIdx.x == 0) sf_diag_times[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
-  Core<WaveGfx950, NB, HP, BM, ZL>::step_body(lds, p, a, cmds, k);
+  Core<WaveGfx950, NB, HP, BM, ZL>::template step_body_t<LOG>(lds, p, a, cmds, k);
 #ifdef SF_DIAG_STAMPS
   __builtin_amdgcn_s_waitcnt(0);  // (the stores have left)
   if (threadIdx.x == 0) sf_diag_times[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memrealtime();
@@ -117,6 +119,84 @@ __global__ void k_done(Params p, uint8_t *out) {
   if (i >= p.A * p.n_agents) return;
   const SF_GLOBAL int32_t *sc = gptr(p.scal) + (size_t)(i / p.n_agents) * SC_WORDS;
   gptr(out)[i] = (uint8_t)(p.auto_reset ? sc[SC_ENDED] : sc[SC_DONE]);
+}
+
+// The episode-log record of an episode that k_reset's first loop top or the second half of a split step ended (at most one
+// per arena and launch), written behind that launch from the state it stored (sf_core.hpp ep_log_late): those two kernels
+// carry no log code of their own.  One wavefront per arena and workgroup (WaveGfx950::lane() is threadIdx.x).
+__global__ __launch_bounds__(64) void k_ep_late(Params p, int after_reset) {
+  Core<WaveGfx950, 1>::ep_log_late(p, (int)blockIdx.x, after_reset != 0);
+}
+
+// Episode log collection (sf_episodes_device): two launches, no host round trip, so that the pair can sit in a captured
+// graph behind the step launches.
+// k_ep_plan: one 1024-thread workgroup, thread t owns a contiguous run of arenas.  Per arena pending = episodes - cursor,
+// kept = min(pending, depth) (the ring holds the newest `depth`), lost = pending - kept.  The exclusive prefix sum of
+// kept over arenas (a wave64 scan of the per-thread sums, then the totals of the waves before) is the arena's first
+// output record; output order is arena ascending, episode ascending.  An arena that meets max_records delivers part or
+// nothing and keeps the rest pending.  Writes the plan [3][A] (first output record, records delivered, first episode
+// delivered), advances each cursor by delivered + lost, and counts = [written, lost, still pending].
+__global__ __launch_bounds__(1024) void k_ep_plan(const int32_t *scal, int32_t *cursor, int A, int depth, int max_records,
+                                                  int32_t *plan, int32_t *counts) {
+  __shared__ int wsum[16];
+  __shared__ int lost_sum;
+  const int t = (int)threadIdx.x, lane = t & 63, w = t >> 6;
+  const int chunk = (A + 1023) / 1024;
+  const int a0 = min(t * chunk, A), a1 = min(a0 + chunk, A);
+  int kept = 0, lost = 0;
+#pragma unroll 4
+  for (int a = a0; a < a1; ++a) {
+    const int pend = max(gptr(scal)[(size_t)a * SC_WORDS + SC_EPISODES] - gptr(cursor)[a], 0);
+    kept += min(pend, depth), lost += pend - min(pend, depth);
+  }
+  int x = kept;  // inclusive scan over the wave
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+#pragma unroll
+  for (int d = 32; d; d >>= 1) lost += __shfl_xor(lost, d, 64);
+  if (t == 0) lost_sum = 0;
+  if (lane == 63) wsum[w] = x;
+  __syncthreads();
+  if (lane == 0) atomicAdd(&lost_sum, lost);
+  int off = x - kept, total = 0;
+  for (int v = 0; v < 16; ++v) {
+    if (v < w) off += wsum[v];
+    total += wsum[v];
+  }
+#pragma unroll 4
+  for (int a = a0; a < a1; ++a) {
+    const int e = gptr(scal)[(size_t)a * SC_WORDS + SC_EPISODES], c = gptr(cursor)[a];
+    const int pend = max(e - c, 0), k = min(pend, depth);
+    const int give = min(max(max_records - off, 0), k);
+    gptr(plan)[a] = off, gptr(plan)[A + a] = give, gptr(plan)[2 * A + a] = e - k;
+    gptr(cursor)[a] = c + (pend - k) + give;
+    off += k;
+  }
+  __syncthreads();
+  if (t == 0) {
+    const int written = min(total, max_records);
+    gptr(counts)[0] = written, gptr(counts)[1] = lost_sum, gptr(counts)[2] = total - written;
+  }
+}
+
+// k_ep_copy: one wavefront per arena (four per workgroup) copies the records the plan gives it out of the ring, the
+// lanes along the record words: each pass stores 64 consecutive dwords of the dense output
+__global__ __launch_bounds__(256) void k_ep_copy(const uint32_t *ring, int A, int depth, int rw, const int32_t *plan,
+                                                 uint32_t *out) {
+  const int a = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
+  if (a >= A) return;
+  const uint32_t n = (uint32_t)gptr(plan)[A + a];
+  if (n == 0u) return;
+  const uint32_t off = (uint32_t)gptr(plan)[a], first = (uint32_t)gptr(plan)[2 * A + a], w = (uint32_t)rw;
+  const SF_GLOBAL uint32_t *src = gptr(ring) + (size_t)a * (size_t)depth * w;
+  SF_GLOBAL uint32_t *dst = gptr(out) + (size_t)off * w;
+  for (uint32_t i = threadIdx.x & 63u; i < n * w; i += 64u) {
+    const uint32_t r = i / w, j = i - r * w;
+    dst[i] = src[(size_t)((first + r) & (uint32_t)(depth - 1)) * w + j];
+  }
 }
 
 constexpr int OBS_W2 = SF_OBS_WINDOW * SF_OBS_WINDOW;  // 961
@@ -909,7 +989,7 @@ struct HipRT {
     }
   }
 
-  template <int NB, bool ZL>
+  template <int NB, bool ZL, bool LOG>
   int do_step(const Params &p, const uint8_t *cmds, int k) {
     // SF_HBM_PLANE_K_MAX=k (A/B switch, default 0 = off): launches of at most k steps leave the flag plane in HBM (the
     // HBM-plane variant, whatever the map's size) instead of staging it — 8 KB less HBM traffic per arena of a one-step
@@ -922,7 +1002,7 @@ struct HipRT {
     const bool hp = hbm_plane(p.cells_pad) || k <= hp_k_max, bm = use_bitmaps(p.cells_pad);
     const size_t lds = hbm_plane(p.cells_pad) || !hp ? lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P)
                                                      : lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P) - (size_t)p.cells_pad;
-    int rc = !hp ? lds_attr(k_step<NB, false, true, ZL>, lds) : bm ? lds_attr(k_step<NB, true, true, ZL>, lds) : lds_attr(k_step<NB, true, false, ZL>, lds);
+    int rc = !hp ? lds_attr(k_step<NB, false, true, ZL, LOG>, lds) : bm ? lds_attr(k_step<NB, true, true, ZL, LOG>, lds) : lds_attr(k_step<NB, true, false, ZL, LOG>, lds);
     if (rc) return rc;
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
     if (timing) {
@@ -941,11 +1021,11 @@ struct HipRT {
       SF_HIP(hipGetLastError());
     }
     if (!hp)
-      hipLaunchKernelGGL((k_step<NB, false, true, ZL>), dim3((unsigned)p.A), dim3(64), lds, stream, p, cmds, k);
+      hipLaunchKernelGGL((k_step<NB, false, true, ZL, LOG>), dim3((unsigned)p.A), dim3(64), lds, stream, p, cmds, k);
     else if (bm)
-      hipLaunchKernelGGL((k_step<NB, true, true, ZL>), dim3((unsigned)p.A), dim3(64), lds, stream, p, cmds, k);
+      hipLaunchKernelGGL((k_step<NB, true, true, ZL, LOG>), dim3((unsigned)p.A), dim3(64), lds, stream, p, cmds, k);
     else
-      hipLaunchKernelGGL((k_step<NB, true, false, ZL>), dim3((unsigned)p.A), dim3(64), lds, stream, p, cmds, k);
+      hipLaunchKernelGGL((k_step<NB, true, false, ZL, LOG>), dim3((unsigned)p.A), dim3(64), lds, stream, p, cmds, k);
     SF_HIP(hipGetLastError());
     if (ev) SF_HIP(hipEventRecord(ev->second, stream));
     return SF_OK;
@@ -960,12 +1040,18 @@ struct HipRT {
   }
   int launch_step(const Params &p, int NB, const uint8_t *cmds, int k) {
     SF_HIP(hipSetDevice(device));
-    if (large_pools(p.Z, p.P)) return do_step<4, true>(p, cmds, k);
+    return ep_log_on ? pick_step<true>(p, NB, cmds, k) : pick_step<false>(p, NB, cmds, k);
+  }
+  // set by the host side while the episode log is on (sf_host.hpp Env::episode_log): k_step's LOG instance is launched
+  bool ep_log_on = false;
+  template <bool LOG>
+  int pick_step(const Params &p, int NB, const uint8_t *cmds, int k) {
+    if (large_pools(p.Z, p.P)) return do_step<4, true, LOG>(p, cmds, k);
     switch (NB) {
-      case 1: return do_step<1, false>(p, cmds, k);
-      case 2: return do_step<2, false>(p, cmds, k);
-      case 3: return do_step<3, false>(p, cmds, k);
-      default: return do_step<4, false>(p, cmds, k);
+      case 1: return do_step<1, false, LOG>(p, cmds, k);
+      case 2: return do_step<2, false, LOG>(p, cmds, k);
+      case 3: return do_step<3, false, LOG>(p, cmds, k);
+      default: return do_step<4, false, LOG>(p, cmds, k);
     }
   }
   template <int NB, bool ZL>
@@ -1007,6 +1093,22 @@ struct HipRT {
     SF_HIP(hipSetDevice(device));
     const int n = p.A * p.n_agents;
     hipLaunchKernelGGL(k_done, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, p, d_out);
+    SF_HIP(hipGetLastError());
+    return SF_OK;
+  }
+  int launch_ep_late(const Params &p, bool after_reset) {
+    SF_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_ep_late, dim3((unsigned)p.A), dim3(64), 0, stream, p, after_reset ? 1 : 0);
+    SF_HIP(hipGetLastError());
+    return SF_OK;
+  }
+  int launch_episodes(const Params &p, const uint32_t *ring, int depth, int32_t *cursor, int32_t *plan, int32_t *out,
+                      int max_records, int32_t *counts) {
+    SF_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_ep_plan, dim3(1), dim3(1024), 0, stream, p.scal, cursor, p.A, depth, max_records, plan, counts);
+    SF_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_ep_copy, dim3((unsigned)((p.A + 3) / 4)), dim3(256), 0, stream, ring, p.A, depth,
+                       ep_record_words(p.n_agents), plan, reinterpret_cast<uint32_t *>(out));
     SF_HIP(hipGetLastError());
     return SF_OK;
   }
@@ -1086,6 +1188,12 @@ struct Comm {
   int32_t *staging[2] = {nullptr, nullptr};
   bool used[2] = {false, false};
   unsigned issued = 0;
+  // the episode-log gather (sf_episodes_allgather): the same double-buffered snapshot, of the raw ring, made on first use
+  hipEvent_t ep_ready[2] = {nullptr, nullptr}, ep_done[2] = {nullptr, nullptr};
+  int32_t *ep_staging[2] = {nullptr, nullptr};
+  size_t ep_words = 0;
+  bool ep_used[2] = {false, false};
+  unsigned ep_issued = 0;
 
   int load() {
     if (dl) return SF_OK;
@@ -1110,7 +1218,34 @@ struct Comm {
       if (done[j]) (void)hipEventDestroy(done[j]), done[j] = nullptr;
       if (staging[j]) (void)hipFree(staging[j]), staging[j] = nullptr;
     }
+    ep_free();
     if (side) (void)hipStreamDestroy(side), side = nullptr;
+  }
+  void ep_free() {
+    for (int j = 0; j < 2; ++j) {
+      if (ep_ready[j]) (void)hipEventDestroy(ep_ready[j]), ep_ready[j] = nullptr;
+      if (ep_done[j]) (void)hipEventDestroy(ep_done[j]), ep_done[j] = nullptr;
+      if (ep_staging[j]) (void)hipFree(ep_staging[j]), ep_staging[j] = nullptr;
+      ep_used[j] = false;
+    }
+    ep_words = 0, ep_issued = 0;
+  }
+  // staging sized for the ring as it is now (sf_episode_log may have changed its depth since the last gather)
+  int ep_prepare(size_t words) {
+    if (ep_words == words) return SF_OK;
+    if (ep_words) SF_HIP(hipStreamSynchronize(side));  // (gathers still reading the old snapshots)
+    ep_free();
+    bool ok = true;
+    for (int j = 0; j < 2 && ok; ++j)
+      ok = hipEventCreateWithFlags(&ep_ready[j], hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&ep_done[j], hipEventDisableTiming) == hipSuccess &&
+           hipMalloc((void **)&ep_staging[j], words * sizeof(int32_t)) == hipSuccess;
+    if (!ok) {
+      ep_free();
+      return fail(SF_ERR_DEVICE, "sf_episodes_allgather: event / staging allocation failed");
+    }
+    ep_words = words;
+    return SF_OK;
   }
 };
 
@@ -1194,6 +1329,22 @@ int sf_results(sf_env *env, int32_t *out_host) {
 int sf_results_device(sf_env *env, int32_t *d_out) {
   SF_ENV(env);
   return env->e.results_device(d_out);
+}
+int sf_episode_log(sf_env *env, int32_t depth) {
+  SF_ENV(env);
+  return env->e.episode_log(depth);
+}
+int sf_episodes(sf_env *env, int32_t *out_host, int32_t max_records, int32_t *counts_host) {
+  SF_ENV(env);
+  return env->e.episodes_host(out_host, max_records, counts_host);
+}
+int sf_episodes_device(sf_env *env, int32_t *d_out, int32_t max_records, int32_t *d_counts) {
+  SF_ENV(env);
+  return env->e.episodes_device(d_out, max_records, d_counts);
+}
+int sf_episode_ring(sf_env *env, int32_t *out_host) {
+  SF_ENV(env);
+  return env->e.episode_ring_host(out_host);
 }
 int sf_done_device(sf_env *env, uint8_t *d_out) {
   SF_ENV(env);
@@ -1319,13 +1470,37 @@ int sf_results_allgather(sf_env *env, int32_t *d_out) {
   c.used[j] = true;
   return SF_OK;
 }
+int sf_episodes_allgather(sf_env *env, int32_t *d_out) {
+  SF_ENV(env);
+  sf::Comm &c = env->comm;
+  if (!c.comm) return sf::fail(SF_ERR_ARG, "sf_comm_init has not been called");
+  if (!d_out) return sf::fail(SF_ERR_ARG, "null gather buffer");
+  if (int rc0 = env->e.episode_log_state("sf_episodes_allgather")) return rc0;
+  SF_HIP(hipSetDevice(env->e.rt.device));
+  const size_t count = env->e.ep_ring_words();
+  if (int rc0 = c.ep_prepare(count)) return rc0;
+  hipStream_t st = env->e.rt.stream;
+  const int j = (int)(c.ep_issued++ & 1u);
+  // as sf_results_allgather: snapshot on the simulation stream, gather on the side stream; the cursors are not touched
+  if (c.ep_used[j]) SF_HIP(hipStreamWaitEvent(st, c.ep_done[j], 0));
+  SF_HIP(hipMemcpyAsync(c.ep_staging[j], env->e.tab.ep_ring, count * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+  SF_HIP(hipEventRecord(c.ep_ready[j], st));
+  SF_HIP(hipStreamWaitEvent(c.side, c.ep_ready[j], 0));
+  int rc = c.nccl(c.all_gather(c.ep_staging[j], d_out, count, 2 /* ncclInt32 */, c.comm, c.side), "ncclAllGather");
+  if (rc) return rc;
+  SF_HIP(hipEventRecord(c.ep_done[j], c.side));
+  c.ep_used[j] = true;
+  return SF_OK;
+}
 int sf_comm_wait(sf_env *env, int32_t host_too) {
   SF_ENV(env);
   sf::Comm &c = env->comm;
   if (!c.comm) return sf::fail(SF_ERR_ARG, "sf_comm_init has not been called");
   SF_HIP(hipSetDevice(env->e.rt.device));
-  for (int j = 0; j < 2; ++j)
+  for (int j = 0; j < 2; ++j) {
     if (c.used[j]) SF_HIP(hipStreamWaitEvent(env->e.rt.stream, c.done[j], 0));
+    if (c.ep_used[j]) SF_HIP(hipStreamWaitEvent(env->e.rt.stream, c.ep_done[j], 0));
+  }
   if (host_too) SF_HIP(hipStreamSynchronize(c.side));
   return SF_OK;
 }

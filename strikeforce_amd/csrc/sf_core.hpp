@@ -1725,6 +1725,9 @@ struct Core {
     return SF_RUNNING;
   }
 
+  // LOG: the instance of k_step launched while the episode log is on (sf_api.hip k_step<.., LOG>).  With the log off the
+  // kernels are the ones built without it: this code is not in them, so their registers and speed are untouched
+  template <bool LOG>
   static SF_DEV void latch_results(const Arena &S, const Params &p, int a) {
     // [kills, teams_kills, loot, damage, effect, Hp, frames, outcome] per agent
     const P ag = W::ltu(W::lane(), (uint32_t)p.n_agents);
@@ -1738,16 +1741,80 @@ struct Core {
     W::gstore(res, base + 5u, S.hhp, ag);
     W::gstore(res, base + 6u, V((uint32_t)S.frame), ag);
     W::gstore(res, base + 7u, V((uint32_t)S.outcome), ag);
+    if (!LOG) return;
+    // the episode log (sf_episode_log), k_step<.., LOG = true> only: the record of the episode check_end has just ended,
+    // into ring slot episode & (depth - 1) (S.episodes is not yet counted up): the arena's header in lanes 0..7, then the
+    // same words as above.  Tables is read only here, in the branch an arena takes once per episode
+    uint32_t *const ring = p.tab->ep_ring;
+    if (ring) {
+      // (word index in 32 bits: sf_episode_log keeps the ring below 2^31 words)
+      const uint32_t depth = (uint32_t)p.tab->ep_depth, rw = (uint32_t)ep_record_words(p.n_agents);
+      const V r = V(((uint32_t)a * depth + ((uint32_t)S.episodes & (depth - 1u))) * rw);
+      V h = V((uint32_t)a);
+      W::setlane(h, 1u, (uint32_t)S.episodes);
+      W::setlane(h, 2u, S.tb_lo), W::setlane(h, 3u, S.tb_hi), W::setlane(h, 4u, S.sr_lo), W::setlane(h, 5u, S.sr_hi);
+      W::setlane(h, 6u, (uint32_t)S.steps), W::setlane(h, 7u, (uint32_t)S.outcome);
+      W::gstore(ring, r + W::lane(), h, W::ltu(W::lane(), (uint32_t)EP_HDR_WORDS));
+      const V b = r + W::lane() * 8u + (uint32_t)EP_HDR_WORDS;
+      W::gstore(ring, b + 0u, S.hk, ag);
+      W::gstore(ring, b + 1u, V((uint32_t)S.tkills), ag);
+      W::gstore(ring, b + 2u, V((uint32_t)S.loot), ag);
+      W::gstore(ring, b + 3u, S.hdm, ag);
+      W::gstore(ring, b + 4u, S.hef, ag);
+      W::gstore(ring, b + 5u, S.hhp, ag);
+      W::gstore(ring, b + 6u, V((uint32_t)S.frame), ag);
+      W::gstore(ring, b + 7u, V((uint32_t)S.outcome), ag);
+    }
+  }
+
+  // k_ep_late, behind k_reset (after_reset) or behind the second half of a split step (k_step_half carries no log code:
+  // inside it the dozen instructions of latch_results<true> cost 14-60 more SGPR spills).  Behind k_reset: every slot of
+  // the arena's ring empty again (all words -1, so episode == -1).  An end at k_reset's first loop top is not logged: the
+  // episode counter does not count it (the arena then stands still, G:1450 before the first iteration), so neither
+  // sf_episodes nor the ring offers it.  Behind a split step: the record of the episode it ended, if any, from what it
+  // stored.  The agent words and the outcome are the latched results; the episode is SC_EPISODES - 1 (the step counted
+  // it); the seed is the stored one, less the reseed stride where auto_reset has moved on to the next episode's; the steps
+  // follow from the latched frame, which is 1 + 2 x steps (G:1441, and every iteration's two half-ticks)
+  static SF_DEV void ep_log_late(const Params &p, int a, bool after_reset) {
+    uint32_t *const ring = p.tab->ep_ring;
+    const int32_t *sc = p.scal + (size_t)a * SC_WORDS;
+    if (!ring) return;
+    const uint32_t depth = (uint32_t)p.tab->ep_depth, rw = (uint32_t)ep_record_words(p.n_agents);
+    if (after_reset) {
+      const uint32_t n = depth * rw;
+      for (uint32_t i = 0u; i < n; i += 64u)
+        W::gstore(ring, W::lane() + i + (uint32_t)a * n, V(0xffffffffu), W::ltu(W::lane() + i, n));
+      return;
+    }
+    if (!W::uload_i32(sc + SC_ENDED)) return;
+    const uint32_t ep = (uint32_t)W::uload_i32(sc + SC_EPISODES) - 1u;
+    uint64_t tb = ((uint64_t)(uint32_t)W::uload_i32(sc + SC_TB_HI) << 32) | (uint32_t)W::uload_i32(sc + SC_TB_LO);
+    if (p.auto_reset) tb -= (uint64_t)(uint32_t)p.reseed;
+    const uint32_t *res = (const uint32_t *)p.results + (size_t)a * (size_t)p.n_agents * 8u;
+    const uint32_t frame = (uint32_t)W::uload_i32((const int32_t *)res + 6), outcome = (uint32_t)W::uload_i32((const int32_t *)res + 7);
+    V h = V((uint32_t)a);
+    W::setlane(h, 1u, ep);
+    W::setlane(h, 2u, (uint32_t)tb), W::setlane(h, 3u, (uint32_t)(tb >> 32));
+    W::setlane(h, 4u, (uint32_t)W::uload_i32(sc + SC_SR_LO)), W::setlane(h, 5u, (uint32_t)W::uload_i32(sc + SC_SR_HI));
+    W::setlane(h, 6u, (frame - 1u) / 2u), W::setlane(h, 7u, outcome);
+    const V r = V(((uint32_t)a * depth + (ep & (depth - 1u))) * rw);
+    W::gstore(ring, r + W::lane(), h, W::ltu(W::lane(), (uint32_t)EP_HDR_WORDS));
+    const uint32_t n = 8u * (uint32_t)p.n_agents;
+    for (uint32_t i = 0u; i < n; i += 64u) {
+      const P in = W::ltu(W::lane() + i, n);
+      W::gstore(ring, r + (uint32_t)EP_HDR_WORDS + W::lane() + i, W::gload(res, W::lane() + i, in), in);
+    }
   }
 
   // top of play()'s while(true): G:1444-1450
+  template <bool LOG = false>
   static SF_DEV void loop_top(Arena &S, uint8_t *lds, const Params &p, int a) {
     SF_PROF(PH_TOP);
     spawns(S, lds, p);
     const int out = check_end(S, p);
     if (out != SF_RUNNING) {
       S.done = 1, S.outcome = out;
-      latch_results(S, p, a);
+      latch_results<LOG>(S, p, a);
     }
   }
 
@@ -1829,7 +1896,7 @@ struct Core {
   // PHASE 0: all of it (the throughput path).  PHASE 1 / 2: the iteration cut where the reference queries the agents of
   // humans other than `ind` (get_command inside human_action, G:988-999): 1 = zombie_action ... the first update_bull
   // (G:1455-1463), 2 = human_action ... the second update_bull and the next loop top (G:1464-1471,1444-1450).
-  template <int PHASE = 0>
+  template <int PHASE = 0, bool LOG = false>
   static SF_DEV void step(Arena &S, uint8_t *lds, const Params &p, int a) {
     if (S.done) return;
     // the two half-ticks share `update_tmp; hit_human; hit_zombie; ++frame; update_bull` (G:1457-1463,1465-1471)
@@ -1873,7 +1940,7 @@ struct Core {
     // the loop top; when the episode ends and auto_reset is on, once more for the episode that begins
     SF_NOUNROLL for (int pass = 0; pass < 2; ++pass) {
       const uint32_t j3 = S.jomle;
-      loop_top(S, lds, p, a);
+      loop_top<LOG>(S, lds, p, a);
       if (pass == 0) S.pd45 = ((S.jomle - j3) & 0xffffu) | (rest << 16);
       if (!S.done || pass == 1) break;
       if (S.ended < 255) ++S.ended;  // episodes that ended during this launch (sf_done with auto_reset)
@@ -2098,8 +2165,16 @@ struct Core {
     store(S, lds, p, a);
   }
 
-  // cmds: [k][A][n_agents]
+  // cmds: [k][A][n_agents].  The gfx950 kernels call step_body_t<LOG> with the instance the host picked; step_body picks
+  // it from Tables at run time, for a runtime that has one code path (the wave emulator of tests/emu)
   static SF_DEV void step_body(uint8_t *lds, const Params &p, int a, const uint8_t *cmds, int k) {
+    if (p.tab->ep_ring)
+      step_body_t<true>(lds, p, a, cmds, k);
+    else
+      step_body_t<false>(lds, p, a, cmds, k);
+  }
+  template <bool LOG>
+  static SF_DEV void step_body_t(uint8_t *lds, const Params &p, int a, const uint8_t *cmds, int k) {
     Arena S;
     // The launch's loads — the two tables, the flag plane's first 4 KB, the arena's state — are all issued before the
     // first of them is waited for: one round trip to memory (two with the generator's log lookup, which needs its state
@@ -2137,7 +2212,7 @@ struct Core {
     for (int s = 0; s < k; ++s) {
       const uint8_t *c = cmds + ((size_t)s * (size_t)p.A + (size_t)a) * (size_t)p.n_agents;
       S.hcmd = W::select(ag, W::gload_u8(c, W::lane(), ag), V((uint32_t)'+'));
-      step(S, lds, p, a);
+      step<0, LOG>(S, lds, p, a);
     }
     SF_STAMP_END(S, a);
     SF_STAMP_STEPPED();

@@ -11,6 +11,8 @@
 #include <string.h>
 
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/strikeforce.h"
@@ -176,6 +178,15 @@ inline uint64_t dg(uint64_t tag, uint64_t idx, int64_t v) {
   return mix64((tag << 56) ^ (idx << 32) ^ (uint64_t)(uint32_t)v ^ ((uint64_t)(v >> 32) << 40));
 }
 
+// whether a runtime has the episode log's own kernels: k_step's LOG instance (chosen through ep_log_on) and k_ep_late (the
+// record behind k_reset and the split step's second half).  The HIP runtime has them; the wave emulator's runtime of
+// tests/emu has one code path (Core::step_body picks the LOG form itself) and no k_ep_late, so there only k_step's
+// records reach the ring
+template <class R, class = void>
+struct has_ep_late : std::false_type {};
+template <class R>
+struct has_ep_late<R, decltype((void)std::declval<R &>().launch_ep_late(std::declval<const Params &>(), true))> : std::true_type {};
+
 template <class RT>
 struct Env {
   sf_config cfg;
@@ -195,6 +206,10 @@ struct Env {
   uint64_t *d_tb = nullptr, *d_serial = nullptr;
   uint8_t *d_cmd = nullptr;
   uint32_t *d_perm = nullptr;  // k_step's launch order (k_rank): arenas by population, for long launches
+  // episode log (sf_episode_log): the ring is tab.ep_ring; per arena the first episode not yet delivered by sf_episodes;
+  // the collection's plan [3][A] (first output record, records delivered, first episode delivered); sf_episodes' staging
+  int32_t *d_ep_cursor = nullptr, *d_ep_plan = nullptr, *d_ep_out = nullptr, *d_ep_counts = nullptr;
+  size_t ep_out_records = 0;
   int balance = 1;             // SF_BALANCE=0 switches the ordering off (A/B measurements)
   int rank_k_min = 8;          // launches of fewer steps run in arena order
   int rank_every = 100;        // steps between two orderings (SF_RANK_EVERY; measured: tools/experiments/README.md)
@@ -359,7 +374,8 @@ struct Env {
 
   void destroy() {
     void *ptrs[] = {d_logt, d_exptab, d_tab, d_map_flags, d_map_pidx, d_map_exits, p.hum, p.zom, p.bul, p.por, p.rng, p.rng2, p.scal, p.results,
-                    p.flags, p.aux_dmg, p.aux_pidx, d_tb, d_serial, d_cmd, d_obs, d_nzprev, d_perm};
+                    p.flags, p.aux_dmg, p.aux_pidx, d_tb, d_serial, d_cmd, d_obs, d_nzprev, d_perm, tab.ep_ring, d_ep_cursor,
+                    d_ep_plan, d_ep_out, d_ep_counts};
     for (void *q : ptrs)
       if (q) rt.free(q);
     rt.shutdown();
@@ -370,8 +386,9 @@ struct Env {
     rt.h2d(d_tb, tb, sizeof(uint64_t) * (size_t)p.A);
     rt.h2d(d_serial, serial, sizeof(uint64_t) * (size_t)p.A);
     rt.zero(p.results, (size_t)p.A * p.n_agents * 8 * sizeof(int32_t));
+    if (tab.ep_ring) rt.zero(d_ep_cursor, (size_t)p.A * sizeof(int32_t));  // (k_ep_late empties the rings)
     int rc = rt.launch_reset(p, NB, d_tb, d_serial);
-    if (rc) return rc;
+    if (rc || (rc = ep_late(true))) return rc;
     was_reset = true;
     mid_step = false;
     steps_since_rank = 1 << 30;
@@ -420,7 +437,7 @@ struct Env {
     if (!d_cmds) return fail(SF_ERR_ARG, "null command array");
     if (!mid_step) return fail(SF_ERR_STATE, "sf_step_end without sf_step_begin");
     int rc = rt.launch_step_half(p, NB, d_cmds, 2);
-    if (rc) return rc;
+    if (rc || (rc = ep_late(false))) return rc;
     mid_step = false;
     return SF_OK;
   }
@@ -500,6 +517,98 @@ struct Env {
     rt.d2d(d_out, p.results, (size_t)p.A * p.n_agents * 8 * sizeof(int32_t));
     return SF_OK;
   }
+  // ---- episode log ------------------------------------------------------------------------------
+  size_t ep_ring_words() const { return (size_t)p.A * (size_t)tab.ep_depth * (size_t)ep_record_words(p.n_agents); }
+  int episode_log(int depth) {
+    if (depth < 0 || depth > 64 || (depth & (depth - 1)))
+      return fail(SF_ERR_ARG, "sf_episode_log: depth must be 0 or a power of two in [1, 64]");
+    if (int rc = not_mid_step("sf_episode_log")) return rc;
+    const size_t A = (size_t)p.A, words = A * (size_t)depth * (size_t)ep_record_words(p.n_agents);
+    if (words >= ((size_t)1 << 31)) return fail(SF_ERR_ARG, "sf_episode_log: ring of 2^31 words or more: lower depth");
+    int rc = rt.sync();  // launches still in flight may write the old ring
+    if (rc) return rc;
+    auto release = [&] {
+      void *old[] = {tab.ep_ring, d_ep_cursor, d_ep_plan, d_ep_out, d_ep_counts};
+      for (void *q : old)
+        if (q) rt.free(q);
+      tab.ep_ring = nullptr, tab.ep_depth = 0;
+      d_ep_cursor = d_ep_plan = d_ep_out = d_ep_counts = nullptr;
+      ep_out_records = 0;
+    };
+    release();
+    if (depth > 0) {
+      if ((rc = alloc(tab.ep_ring, words)) || (rc = alloc(d_ep_cursor, A)) || (rc = alloc(d_ep_plan, 3 * A)) ||
+          (rc = alloc(d_ep_counts, 3))) {
+        release();  // (the device's Tables must not keep a freed ring: the log is off after a failure)
+        rt.h2d(d_tab, &tab, sizeof tab);
+        if constexpr (has_ep_late<RT>::value) rt.ep_log_on = false;
+        rt.sync();
+        return rc;
+      }
+      tab.ep_depth = depth;
+      // every slot empty (episode -1); the cursors start at the episodes counted so far: only later ones are offered
+      std::vector<uint32_t> fill(words, 0xffffffffu);
+      std::vector<int32_t> sc(A * SC_WORDS), cur(A);
+      rt.h2d(tab.ep_ring, fill.data(), words * sizeof(uint32_t));
+      rt.d2h(sc.data(), p.scal, sc.size() * sizeof(int32_t));
+      if ((rc = rt.sync())) return rc;
+      for (size_t a = 0; a < A; ++a) cur[a] = sc[a * SC_WORDS + SC_EPISODES];
+      rt.h2d(d_ep_cursor, cur.data(), A * sizeof(int32_t));
+    }
+    rt.h2d(d_tab, &tab, sizeof tab);
+    if constexpr (has_ep_late<RT>::value) rt.ep_log_on = tab.ep_ring != nullptr;
+    return rt.sync();  // (the staging vectors and `tab` stay untouched until the copies are done)
+  }
+  int ep_late(bool after_reset) {
+    if (!tab.ep_ring) return SF_OK;
+    if constexpr (has_ep_late<RT>::value) {
+      return rt.launch_ep_late(p, after_reset);
+    } else if (after_reset) {  // (the emulator's runtime: the rings are at least emptied)
+      std::vector<uint32_t> fill(ep_ring_words(), 0xffffffffu);
+      rt.h2d(tab.ep_ring, fill.data(), fill.size() * sizeof(uint32_t));
+      return rt.sync();
+    }
+    return SF_OK;
+  }
+  int episode_log_state(const char *what) const {
+    if (!tab.ep_ring) return fail(SF_ERR_STATE, std::string(what) + ": the episode log is off (sf_episode_log)");
+    return not_mid_step(what);
+  }
+  int episodes_device(int32_t *d_out, int max_records, int32_t *d_counts) {
+    if (int rc = episode_log_state("sf_episodes_device")) return rc;
+    if (max_records < 0) return fail(SF_ERR_ARG, "sf_episodes_device: max_records must not be negative");
+    if ((!d_out && max_records > 0) || !d_counts) return fail(SF_ERR_ARG, "null buffer");
+    return rt.launch_episodes(p, tab.ep_ring, tab.ep_depth, d_ep_cursor, d_ep_plan, d_out, max_records, d_counts);
+  }
+  int episodes_host(int32_t *out, int max_records, int32_t *counts) {
+    if (int rc = episode_log_state("sf_episodes")) return rc;
+    if (max_records < 0) return fail(SF_ERR_ARG, "sf_episodes: max_records must not be negative");
+    if ((!out && max_records > 0) || !counts) return fail(SF_ERR_ARG, "null buffer");
+    const size_t rw = (size_t)ep_record_words(p.n_agents), cap = (size_t)p.A * (size_t)tab.ep_depth;
+    const size_t n = (size_t)max_records < cap ? (size_t)max_records : cap;  // more than the ring holds is never written
+    int rc;
+    if (n > ep_out_records) {
+      if ((rc = rt.sync())) return rc;
+      if (d_ep_out) rt.free(d_ep_out), d_ep_out = nullptr, ep_out_records = 0;
+      if ((rc = alloc(d_ep_out, n * rw))) return rc;
+      ep_out_records = n;
+    }
+    if ((rc = episodes_device(d_ep_out, (int)n, d_ep_counts))) return rc;
+    rt.d2h(counts, d_ep_counts, 3 * sizeof(int32_t));
+    if ((rc = rt.sync())) return rc;
+    if (counts[0] > 0) {
+      rt.d2h(out, d_ep_out, (size_t)counts[0] * rw * sizeof(int32_t));
+      rc = rt.sync();
+    }
+    return rc;
+  }
+  int episode_ring_host(int32_t *out) {
+    if (!out) return fail(SF_ERR_ARG, "null output buffer");
+    if (int rc = episode_log_state("sf_episode_ring")) return rc;
+    rt.d2h(out, tab.ep_ring, ep_ring_words() * sizeof(int32_t));
+    return rt.sync();
+  }
+
   int done_host(uint8_t *out) {
     if (!out) return fail(SF_ERR_ARG, "null done buffer");
     if (int rc0 = not_mid_step("sf_done")) return rc0;

@@ -103,7 +103,16 @@ struct Tables {
   float class_rec[8][32];
   uint32_t class_mask[8];
   uint32_t hatab[HT_WORDS_MAX];  // see HT_* above; the used part (Params::ht_bytes) is copied to LDS by every launch
+  // episode log (sf_episode_log): [A][ep_depth][ep_record_words(n_agents)] records of finished episodes, null while off.
+  // Read by k_step only where an episode ends (sf_core.hpp ep_log), and by k_ep_late; here rather than in Params, whose
+  // layout every kernel's argument offsets and register allocation depend on
+  uint32_t *ep_ring;
+  int32_t ep_depth;  // power of two in [1, 64]; 0 = off
 };
+// one record of the episode log: arena, episode, tb_lo, tb_hi, serial_lo, serial_hi, steps, outcome; then per agent the
+// eight words of sf_results
+constexpr int EP_HDR_WORDS = 8;
+SF_HD inline int ep_record_words(int n_agents) { return EP_HDR_WORDS + 8 * n_agents; }
 
 // ---- everything a kernel needs -----------------------------------------------------------------------
 struct Params {

@@ -53,6 +53,14 @@ def load_library():
         if hasattr(L, "sf_done_view_device"):  # (A/B runs against older builds of the library, tools/ab.sh)
             L.sf_done_view_device.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
             L.sf_done_view_device.restype = C.c_int
+        if hasattr(L, "sf_episode_log"):  # (the episode log; an older build loaded through SF_LIBRARY_PATH lacks it)
+            L.sf_episode_log.argtypes = [vp, C.c_int32]
+            L.sf_episodes.argtypes = [vp, vp, C.c_int32, vp]
+            L.sf_episodes_device.argtypes = [vp, vp, C.c_int32, vp]
+            L.sf_episode_ring.argtypes = [vp, vp]
+            L.sf_episodes_allgather.argtypes = [vp, vp]
+            for n in ("sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather"):
+                getattr(L, n).restype = C.c_int
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -81,7 +89,29 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_observe_device", "sf_observe_device_delta", "sf_observe_sparse_device", "sf_observe_overflow_device", "sf_results", "sf_results_device", "sf_done", "sf_done_device", "sf_done_view_device", "sf_state_digest", "sf_dump_arena",
            "sf_set_stream", "sf_synchronize", "sf_kernel_time", "sf_last_error", "sf_abi_version",
            "sf_comm_unique_id", "sf_comm_init", "sf_results_allgather", "sf_comm_wait", "sf_comm_ranks",
-           "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws"]
+           "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
+           "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather"]
+
+EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
+
+
+def episode_record_words(n_agents):
+    """int32 words of one episode-log record: the header, then eight result words per agent."""
+    return EPISODE_HDR_WORDS + 8 * n_agents
+
+
+def decode_episodes(records, n_agents):
+    """Named arrays of episode-log records (sf_episodes / sf_episode_ring / sf_episodes_allgather output, any leading
+    shape, flattened to n records): arena, episode, tb (uint64), serial (uint64), steps, outcome (int32 [n]) and
+    results (int32 [n][n_agents][8], the words sf_results holds).  Empty ring slots come out with episode == -1."""
+    r = np.ascontiguousarray(records, dtype=np.int32).reshape(-1, episode_record_words(n_agents))
+    u = r.view(np.uint32).astype(np.uint64)
+    return {
+        "arena": r[:, 0].copy(), "episode": r[:, 1].copy(),
+        "tb": u[:, 2] | (u[:, 3] << np.uint64(32)), "serial": u[:, 4] | (u[:, 5] << np.uint64(32)),
+        "steps": r[:, 6].copy(), "outcome": r[:, 7].copy(),
+        "results": r[:, EPISODE_HDR_WORDS:].reshape(-1, n_agents, 8).copy(),
+    }
 
 
 class ArenaBatch:
@@ -225,6 +255,52 @@ class ArenaBatch:
 
     def comm_wait(self, host_too=False):
         self._ck(self.L.sf_comm_wait(self.h, 1 if host_too else 0), "sf_comm_wait")
+
+    # ---- episode log (strikeforce.h sf_episode_log) ----
+    @property
+    def episode_record_words(self):
+        return episode_record_words(self.cfg.n_agents)
+
+    def _need_log(self):
+        if not hasattr(self.L, "sf_episode_log"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no episode log")
+
+    def enable_episode_log(self, depth):
+        """Keep the last `depth` (a power of two in [1, 64]) finished episodes of every arena in a device ring; 0 turns
+        the log off.  Only episodes that end from now on are offered."""
+        self._need_log()
+        self._ck(self.L.sf_episode_log(self.h, int(depth)), "sf_episode_log")
+        self.episode_depth = int(depth)
+
+    def episodes(self, max_records=None):
+        """The finished episodes not delivered yet: (records int32 [n][record words], (written, lost, pending)).
+        max_records=None: as many as the rings can hold."""
+        self._need_log()
+        if max_records is None:
+            max_records = self.cfg.arenas * getattr(self, "episode_depth", 64)
+        out = np.zeros((max(int(max_records), 0), self.episode_record_words), dtype=np.int32)
+        counts = np.zeros(3, dtype=np.int32)
+        self._ck(self.L.sf_episodes(self.h, C.c_void_p(out.ctypes.data), int(max_records), C.c_void_p(counts.ctypes.data)),
+                 "sf_episodes")
+        return out[:counts[0]], (int(counts[0]), int(counts[1]), int(counts[2]))
+
+    def episodes_device(self, d_out_ptr, max_records, d_counts_ptr):
+        """The same on the device, no host synchronisation: d_out int32 [max_records][record words], d_counts int32 [3]."""
+        self._need_log()
+        self._ck(self.L.sf_episodes_device(self.h, C.c_void_p(d_out_ptr), int(max_records), C.c_void_p(d_counts_ptr)),
+                 "sf_episodes_device")
+
+    def episode_ring(self):
+        """The raw rings, int32 [arenas][depth][record words]; empty slots have episode == -1."""
+        self._need_log()
+        out = np.zeros((self.cfg.arenas, getattr(self, "episode_depth", 0), self.episode_record_words), dtype=np.int32)
+        self._ck(self.L.sf_episode_ring(self.h, C.c_void_p(out.ctypes.data)), "sf_episode_ring")
+        return out
+
+    def episodes_allgather(self, d_out_ptr):
+        """RCCL all-gather of every rank's raw rings into [world][arenas][depth][record words] int32, on a side stream."""
+        self._need_log()
+        self._ck(self.L.sf_episodes_allgather(self.h, C.c_void_p(d_out_ptr)), "sf_episodes_allgather")
 
     def done_device(self, d_out_ptr):
         """check_end()'s verdict on the device, one byte per (arena, agent): what PolicyBatch.reset_memory takes."""

@@ -1,0 +1,114 @@
+"""The episode log's k_step part (sf_core.hpp latch_results<true>, the code of the k_step instance launched while the log
+is on) on the CPU wave emulator: the device core runs in K = 100 step launches with the log on, and after every launch its
+raw rings must equal what the oracle, stepped one step at a time, says: each finished episode's sfo_results behind its
+header, episode e in slot e & (depth - 1).  The shim (tests/episode_log/sf_emu_episodes.cpp) is tests/emu's build plus
+sf_episode_log / sf_episode_ring.  k_ep_late (the split step's records, the rings emptied by sf_reset on the device) has
+no emulator counterpart: tests/test_gpu_episode_log.py covers it."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import emu_lib
+from episode_log_ref import OracleEpisodes
+from oracle_lib import Oracle
+from strikeforce_amd import abi, config, env
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SF_ERR_ARG = -1
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("episode_log") / "libsf_emu_episodes.so")
+    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-shared",
+                           "-o", so, os.path.join(ROOT, "tests", "episode_log", "sf_emu_episodes.cpp")])
+    L = C.CDLL(so)
+    L.sfe_create.argtypes = [C.POINTER(abi.Config)]
+    L.sfe_create.restype = C.c_void_p
+    abi.bind(L, "sfe_")
+    L.sfe_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.sfe_last_error.restype = C.c_char_p
+    L.sfe_episode_log.argtypes = [C.c_void_p, C.c_int32]
+    L.sfe_episode_ring.argtypes = [C.c_void_p, C.c_void_p]
+    return L
+
+
+class EmuLog(emu_lib.Emu):
+    def __init__(self, workload, L):  # (emu_lib.Emu's surface over the shim's library)
+        self.w, self.cfg, self.L = workload, workload.cfg, L
+        self.h = L.sfe_create(C.byref(self.cfg))
+        assert self.h, L.sfe_last_error().decode()
+
+    def episode_log(self, depth):
+        return self.L.sfe_episode_log(self.h, depth)
+
+    def ring(self, depth):
+        out = np.zeros((self.cfg.arenas, depth, env.episode_record_words(self.cfg.n_agents)), dtype=np.int32)
+        assert self.L.sfe_episode_ring(self.h, out.ctypes.data) == 0
+        return out
+
+
+def workload(which, arenas):
+    w = config.baseline_workload(which, arenas=arenas)
+    if which == "C3":
+        w.cfg.timer_frames_per_level = 30  # every Timer episode ends at frame 31 unless the player dies first
+    w.cfg.reseed_stride = 1000
+    return w
+
+
+@pytest.mark.parametrize("which,arenas,steps,depth", [("C3", 6, 400, 8), ("C3", 4, 300, 2), ("C2", 8, 1200, 8)])
+def test_emulated_rings_equal_the_oracle_after_every_launch(shim, which, arenas, steps, depth):
+    w = workload(which, arenas)
+    e = EmuLog(w, shim)
+    assert e.episode_log(depth) == 0
+    tb, sr = w.seeds()
+    e.reset(tb, sr)
+    o = OracleEpisodes(Oracle(w), tb, sr)
+    assert (e.ring(depth) == -1).all()
+    cmds, _ = config.bench_commands(arenas, 1, steps)
+    several = False
+    for s0 in range(0, steps, 100):
+        before = o.ended()
+        e.step_many(cmds[s0:s0 + 100])
+        for s in range(s0, s0 + 100):
+            o.step(cmds[s])
+        several |= bool((o.ended() - before >= 2).any())
+        got, want = e.ring(depth), o.ring(depth)
+        assert (got == want).all(), np.argwhere(got != want)[:5]
+    if which == "C3":  # the case the log exists for (C2: data-dependent ends, fewer of them)
+        assert o.ended().min() >= 2 and several
+    assert o.ended().sum() >= 1
+    # the newest record of every arena is what sf_results latched
+    res = e.results()
+    for a in range(arenas):
+        n = o.ended()[a]
+        if n == 0:
+            continue
+        assert (e.ring(depth)[a, (n - 1) & (depth - 1), env.EPISODE_HDR_WORDS:] == res[a].reshape(-1)).all()
+    # a second sf_reset empties the rings, and the first episode is 0 again
+    e.reset(tb, sr)
+    assert (e.ring(depth) == -1).all()
+    o2 = OracleEpisodes(Oracle(w), tb, sr)
+    e.step_many(cmds[:100])
+    for s in range(100):
+        o2.step(cmds[s])
+    assert (e.ring(depth) == o2.ring(depth)).all()
+    e.close()
+
+
+def test_log_off_leaves_the_emulated_core_as_it_was(shim):
+    w = workload("C2", 4)
+    a, b = EmuLog(w, shim), emu_lib.Emu(w)
+    assert a.episode_log(4) == 0
+    tb, sr = w.seeds()
+    a.reset(tb, sr), b.reset(tb, sr)
+    cmds, _ = config.bench_commands(4, 1, 300)
+    for s0 in range(0, 300, 100):
+        a.step_many(cmds[s0:s0 + 100]), b.step_many(cmds[s0:s0 + 100])
+        assert (a.digest() == b.digest()).all() and (a.results() == b.results()).all() and (a.done() == b.done()).all()
+    assert a.episode_log(3) == SF_ERR_ARG and a.episode_log(128) == SF_ERR_ARG
+    assert a.episode_log(0) == 0
+
