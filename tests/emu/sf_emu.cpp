@@ -15,42 +15,53 @@
 
 namespace sf {
 
+// the template arguments <NB, HP, BM, ZL> of the last launch of each kernel (sfe_last_variant): what the suite's own
+// restatement of the choice (tests/variant_cases.py expected_variant) is checked against
+enum { LV_RESET = 0, LV_STEP, LV_STEP_HALF, LV_KINDS };
+struct Variant {
+  int32_t nb = 0, hp = 0, bm = 0, zl = 0;
+};
+template <int NB, bool HP, bool BM, bool ZL>
+static void note(Variant &v) {
+  v.nb = NB, v.hp = HP, v.bm = BM, v.zl = ZL;
+}
+
 // same variant choice as the HIP launchers: big flag planes stay in "HBM" (here: the host arrays)
 template <int NB, bool ZL>
-static void run_reset(const Params &p, const uint64_t *tb, const uint64_t *serial) {
+static void run_reset(const Params &p, const uint64_t *tb, const uint64_t *serial, Variant &v) {
   std::vector<uint8_t> lds(lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P));
   for (int a = 0; a < p.A; ++a) {
     if (!hbm_plane(p.cells_pad))
-      Core<WaveEmu, NB, false, true, ZL>::reset_body(lds.data(), p, a, tb, serial);
+      Core<WaveEmu, NB, false, true, ZL>::reset_body(lds.data(), p, a, tb, serial), note<NB, false, true, ZL>(v);
     else if (use_bitmaps(p.cells_pad))
-      Core<WaveEmu, NB, true, true, ZL>::reset_body(lds.data(), p, a, tb, serial);
+      Core<WaveEmu, NB, true, true, ZL>::reset_body(lds.data(), p, a, tb, serial), note<NB, true, true, ZL>(v);
     else
-      Core<WaveEmu, NB, true, false, ZL>::reset_body(lds.data(), p, a, tb, serial);
+      Core<WaveEmu, NB, true, false, ZL>::reset_body(lds.data(), p, a, tb, serial), note<NB, true, false, ZL>(v);
   }
 }
 template <int NB, bool ZL>
-static void run_step(const Params &p, const uint8_t *cmds, int k) {
+static void run_step(const Params &p, const uint8_t *cmds, int k, Variant &v) {
   std::vector<uint8_t> lds(lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P));
   for (int a = 0; a < p.A; ++a) {
     if (!hbm_plane(p.cells_pad))
-      Core<WaveEmu, NB, false, true, ZL>::step_body(lds.data(), p, a, cmds, k);
+      Core<WaveEmu, NB, false, true, ZL>::step_body(lds.data(), p, a, cmds, k), note<NB, false, true, ZL>(v);
     else if (use_bitmaps(p.cells_pad))
-      Core<WaveEmu, NB, true, true, ZL>::step_body(lds.data(), p, a, cmds, k);
+      Core<WaveEmu, NB, true, true, ZL>::step_body(lds.data(), p, a, cmds, k), note<NB, true, true, ZL>(v);
     else
-      Core<WaveEmu, NB, true, false, ZL>::step_body(lds.data(), p, a, cmds, k);
+      Core<WaveEmu, NB, true, false, ZL>::step_body(lds.data(), p, a, cmds, k), note<NB, true, false, ZL>(v);
   }
 }
 
 template <int NB, bool ZL>
-static void run_step_half(const Params &p, const uint8_t *cmds, int phase) {
+static void run_step_half(const Params &p, const uint8_t *cmds, int phase, Variant &v) {
   std::vector<uint8_t> lds(lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P));
   for (int a = 0; a < p.A; ++a) {
     if (!hbm_plane(p.cells_pad))
-      Core<WaveEmu, NB, false, true, ZL>::step_half_body(lds.data(), p, a, cmds, phase);
+      Core<WaveEmu, NB, false, true, ZL>::step_half_body(lds.data(), p, a, cmds, phase), note<NB, false, true, ZL>(v);
     else if (use_bitmaps(p.cells_pad))
-      Core<WaveEmu, NB, true, true, ZL>::step_half_body(lds.data(), p, a, cmds, phase);
+      Core<WaveEmu, NB, true, true, ZL>::step_half_body(lds.data(), p, a, cmds, phase), note<NB, true, true, ZL>(v);
     else
-      Core<WaveEmu, NB, true, false, ZL>::step_half_body(lds.data(), p, a, cmds, phase);
+      Core<WaveEmu, NB, true, false, ZL>::step_half_body(lds.data(), p, a, cmds, phase), note<NB, true, false, ZL>(v);
   }
 }
 
@@ -105,6 +116,7 @@ static void run_observe(const Params &p, float *out) {
 }
 
 struct CpuRT {
+  Variant last[LV_KINDS];
   int init(int) { return SF_OK; }
   void shutdown() {}
   size_t max_lds() const { return 160 * 1024; }
@@ -117,27 +129,27 @@ struct CpuRT {
   int sync() { return SF_OK; }
   int launch_reset(const Params &p, int NB, const uint64_t *tb, const uint64_t *serial) {
     if (large_pools(p.Z, p.P)) {
-      run_reset<4, true>(p, tb, serial);
+      run_reset<4, true>(p, tb, serial, last[LV_RESET]);
       return SF_OK;
     }
     switch (NB) {
-      case 1: run_reset<1, false>(p, tb, serial); break;
-      case 2: run_reset<2, false>(p, tb, serial); break;
-      case 3: run_reset<3, false>(p, tb, serial); break;
-      default: run_reset<4, false>(p, tb, serial); break;
+      case 1: run_reset<1, false>(p, tb, serial, last[LV_RESET]); break;
+      case 2: run_reset<2, false>(p, tb, serial, last[LV_RESET]); break;
+      case 3: run_reset<3, false>(p, tb, serial, last[LV_RESET]); break;
+      default: run_reset<4, false>(p, tb, serial, last[LV_RESET]); break;
     }
     return SF_OK;
   }
   int launch_step(const Params &p, int NB, const uint8_t *cmds, int k) {
     if (large_pools(p.Z, p.P)) {
-      run_step<4, true>(p, cmds, k);
+      run_step<4, true>(p, cmds, k, last[LV_STEP]);
       return SF_OK;
     }
     switch (NB) {
-      case 1: run_step<1, false>(p, cmds, k); break;
-      case 2: run_step<2, false>(p, cmds, k); break;
-      case 3: run_step<3, false>(p, cmds, k); break;
-      default: run_step<4, false>(p, cmds, k); break;
+      case 1: run_step<1, false>(p, cmds, k, last[LV_STEP]); break;
+      case 2: run_step<2, false>(p, cmds, k, last[LV_STEP]); break;
+      case 3: run_step<3, false>(p, cmds, k, last[LV_STEP]); break;
+      default: run_step<4, false>(p, cmds, k, last[LV_STEP]); break;
     }
     return SF_OK;
   }
@@ -145,14 +157,14 @@ struct CpuRT {
   int launch_rank(const Params &, uint32_t *) { return SF_OK; }
   int launch_step_half(const Params &p, int NB, const uint8_t *cmds, int phase) {
     if (large_pools(p.Z, p.P)) {
-      run_step_half<4, true>(p, cmds, phase);
+      run_step_half<4, true>(p, cmds, phase, last[LV_STEP_HALF]);
       return SF_OK;
     }
     switch (NB) {
-      case 1: run_step_half<1, false>(p, cmds, phase); break;
-      case 2: run_step_half<2, false>(p, cmds, phase); break;
-      case 3: run_step_half<3, false>(p, cmds, phase); break;
-      default: run_step_half<4, false>(p, cmds, phase); break;
+      case 1: run_step_half<1, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
+      case 2: run_step_half<2, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
+      case 3: run_step_half<3, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
+      default: run_step_half<4, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
     }
     return SF_OK;
   }
@@ -235,4 +247,11 @@ int sfe_dump_arena(sfe_env *env, int32_t a, sf_arena_hdr *hdr, sf_human_rec *hs,
   return env->e.dump_arena(a, hdr, hs, zs, bs, ps, cf, cd, cp);
 }
 const char *sfe_last_error(void) { return sf::last_error().c_str(); }
+// out[4] = NB, HP, BM, ZL of the last launch of kernel `kind` (0 reset, 1 step, 2 half step); all 0 before the first
+int sfe_last_variant(sfe_env *env, int32_t kind, int32_t *out) {
+  if (kind < 0 || kind >= sf::LV_KINDS) return SF_ERR_ARG;
+  const sf::Variant &v = env->e.rt.last[kind];
+  out[0] = v.nb, out[1] = v.hp, out[2] = v.bm, out[3] = v.zl;
+  return SF_OK;
+}
 }

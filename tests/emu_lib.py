@@ -23,6 +23,7 @@ def lib(asan=False):
         abi.bind(L, "sfe_")
         L.sfe_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
         L.sfe_last_error.restype = C.c_char_p
+        L.sfe_last_variant.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         _LIBS[name] = L
     return _LIBS[name]
 
@@ -99,3 +100,12 @@ class Emu:
 
     def dump(self, arena):
         return dump_with(self.L.sfe_dump_arena, self.h, self.cfg, arena)
+
+    KINDS = {"reset": 0, "step": 1, "step_half": 2}
+
+    def last_variant(self, kind):
+        """(NB, HP, BM, ZL): the template arguments of the last launch of k_reset / k_step / k_step_half ("reset",
+        "step", "step_half"), as the device's launchers would pick them; (0, 0, 0, 0) before the first."""
+        out = (C.c_int32 * 4)()
+        assert self.L.sfe_last_variant(self.h, self.KINDS[kind], out) == 0
+        return tuple(out)
