@@ -142,12 +142,15 @@ def _gru(x, h, w_ih, w_hh, b_ih, b_hh):
 
 
 @torch.no_grad()
-def forward_batched(params, obs, h, action_input):
-    """obs [B,32,31,31], h [2,B,160], action_input [B,9] (numpy or tensors) -> probs [B,9], value [B], new h [2,B,160]."""
-    P = {k: torch.as_tensor(np.asarray(v), dtype=torch.float32) for k, v in params.items()}
-    x = torch.as_tensor(obs, dtype=torch.float32)
-    h = torch.as_tensor(h, dtype=torch.float32)
-    a = torch.as_tensor(action_input, dtype=torch.float32)
+def forward_batched(params, obs, h, action_input, dtype=torch.float32):
+    """obs [B,32,31,31], h [2,B,160], action_input [B,9] (numpy or tensors) -> probs [B,9], value [B], new h [2,B,160].
+    dtype=torch.float64: parameters, observation, state and one-hot are converted up front and every operation runs in
+    f64 (the results are f64 arrays): the same function with roundings 2^29 times smaller, what tests measure both the
+    f32 form and the HIP kernels against (tests/test_policy_ref64.py, tests/test_gpu_policy_edges.py)."""
+    P = {k: torch.as_tensor(np.asarray(v), dtype=dtype) for k, v in params.items()}
+    x = torch.as_tensor(obs, dtype=dtype)
+    h = torch.as_tensor(h, dtype=dtype)
+    a = torch.as_tensor(action_input, dtype=dtype)
     B = x.shape[0]
     y = x
     for i in range(4):

@@ -23,7 +23,7 @@ import policy_ref  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 # |hip - torch| <= ATOL + RTOL * |torch| on probabilities, value and the recurrent state
-RTOL, ATOL = 5e-5, 1e-6
+from policy_cases import ATOL, RTOL  # noqa: E402  (shared with tests/test_gpu_policy_edges.py)
 
 
 def _obs(rng, B):
