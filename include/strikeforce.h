@@ -47,7 +47,8 @@ extern "C" {
 enum { SF_MODE_SOLO = 0, SF_MODE_TIMER = 1, SF_MODE_SQUAD = 2, SF_MODE_BATTLE = 3 };
 
 /* Episode outcome codes written to sf_results()[..][7] — gameplay.hpp:1102-1229 (check_end). */
-enum { SF_RUNNING = 0, SF_DIED = 1, SF_WON = 2, SF_TIME_LOST = 3, SF_TIME_WON = 4, SF_QUIT = 5 };
+enum { SF_RUNNING = 0, SF_DIED = 1, SF_WON = 2, SF_TIME_LOST = 3, SF_TIME_WON = 4, SF_QUIT = 5,
+       SF_SAMPLE_END = 6 /* not an outcome of check_end: a replayed arena whose command stream ran out (sf_replay_step) */ };
 
 /* Status codes (API misuse only; gameplay "failures" stay silent no-ops as in the reference). */
 enum {
@@ -273,6 +274,47 @@ int sf_episodes_device(sf_env *env, int32_t *d_out, int32_t max_records, int32_t
 /* The raw rings, out [arenas][depth][record] int32 (episode e of an arena in slot e & (depth - 1)); empty slots have
  * episode == -1.  Leaves the cursors alone. */
 int sf_episode_ring(sf_env *env, int32_t *out_host);
+
+/* ---- replay of logged games: per-arena command streams, fetched on the device ------------------------------------
+ * The reference replays a logged game (`.sf_sample`, include/sf_sample.hpp) by reading its commands back inside the
+ * loop: `replay_file >> command[ind]` at the head of human_action (gameplay.hpp:968-969) and, in a match, one
+ * `replay_file >> command[i]` for every other human with mh[i] && remote[i], slots ascending (gameplay.hpp:979-986;
+ * the file is opened and its header read in load_data, gameplay.hpp:1749-1806).  How many lines an iteration takes thus
+ * depends on who is still alive after the first half of that very iteration (gameplay.hpp:1455-1463), so the lines
+ * cannot be laid out beforehand as [k][arenas][n_agents]: they are fetched where the state is.
+ *
+ * sf_replay_load: one stream of command chars per arena, in file order; arena a owns streams[offsets[a] ..
+ * offsets[a + 1]) (host memory, offsets [arenas + 1] non-decreasing, less than 4 GiB in all).  Uploads them and puts every
+ * cursor at its stream's start.  Needs auto_reset == 0 (SF_ERR_STATE otherwise); the seeds are sf_reset's, which also
+ * rewinds the streams.  sf_replay_load(env, NULL, NULL) frees everything; while nothing is loaded nothing is allocated
+ * and no other entry point behaves differently.
+ *
+ * sf_replay_step: one iteration of every arena with the commands taken from the streams on the device, no host
+ * synchronisation: a loop-top check, the first half of the iteration (as sf_step_begin), the fetch, the second half (as
+ * sf_step_end_device) — two small launches more than the split step.  Per arena:
+ *   - loop top: an arena whose game has ended (check_end, gameplay.hpp:1450) stands still as ever, state GAME_ENDED, the
+ *     rest of its stream unread.  Otherwise, if the cursor has reached the stream's length, the arena stops exactly as a
+ *     finished game without auto_reset does — done = 1, outcome = SF_SAMPLE_END, sf_done = 1, the state as the last
+ *     iteration left it (sf_dump_arena / sf_state_digest give the replay's final world) — state SAMPLE_ENDED.  This is not
+ *     an episode: sf_arena_hdr.episodes does not move, sf_results is not latched, the episode log gets no record.
+ *     Otherwise the next line is the command of `ind`.
+ *   - between the halves: every commanded human g != ind that sf_agent_alive would report (alive and still commanded; a
+ *     dead player's slot re-used by a spawned NPC is not) takes the next line, slots ascending.  Where the stream ends in
+ *     the middle of this, the humans without a line obey '+' (what the reference's failed read leaves in command[i],
+ *     gameplay.hpp:1009), the state becomes TRUNCATED and the arena stops at the next loop top like SAMPLE_ENDED.
+ * sf_replay_status: per arena 4 x int32: state (SF_REPLAY_*), cursor (lines taken), iterations played, 0.
+ * sf_replay_commands_device: uint8 [arenas][n_agents], the line each commanded human took in the LAST iteration, 0 where
+ * it took none (dead, gone, arena stopped).  With an sf_observe* call in front of sf_replay_step this is the
+ * (observation, action) pair a replay_mode Agent of `ind` sees: bot() at the loop top (gameplay.hpp:955-958), update() in
+ * human_action (gameplay.hpp:970-975).  The other players' mid-iteration observations are not part of this call: a caller
+ * who wants them keeps to sf_step_begin / sf_observe / sf_step_end and feeds the lines itself.
+ * SF_ERR_STATE: nothing loaded, before sf_reset, or between sf_step_begin and sf_step_end. */
+enum { SF_REPLAY_RUNNING = 0, SF_REPLAY_GAME_ENDED = 1, SF_REPLAY_SAMPLE_ENDED = 2, SF_REPLAY_TRUNCATED = 3 };
+int sf_replay_load(sf_env *env, const uint8_t *streams, const int64_t *offsets);
+int sf_replay_step(sf_env *env);
+int sf_replay_status(sf_env *env, int32_t *out_host);
+int sf_replay_status_device(sf_env *env, int32_t *d_out);
+int sf_replay_commands_device(sf_env *env, uint8_t *d_out);
 
 /* ---- multi-GPU: the one exchange step ------------------------------------------
  * Arenas are sharded over one sf_env per GPU with no data-path collective.  The result records of all shards are

@@ -18,6 +18,9 @@ MAX_AGENTS = 16
 
 MODE_SOLO, MODE_TIMER, MODE_SQUAD, MODE_BATTLE = 0, 1, 2, 3
 RUNNING, DIED, WON, TIME_LOST, TIME_WON, QUIT = 0, 1, 2, 3, 4, 5
+SAMPLE_END = 6  # SF_SAMPLE_END: a replayed arena whose command stream ran out (sf_replay_step)
+REPLAY_RUNNING, REPLAY_GAME_ENDED, REPLAY_SAMPLE_ENDED, REPLAY_TRUNCATED = 0, 1, 2, 3  # SF_REPLAY_*
+REPLAY_STATES = ("running", "game ended", "sample ended", "truncated")
 
 CELL_WALL, CELL_TEMP, CELL_PIN_UP, CELL_PIN_DN, CELL_POUT, CELL_CHEST = 1, 2, 4, 8, 16, 32
 CELL_CONS_SHIFT = 6

@@ -128,6 +128,12 @@ __global__ __launch_bounds__(64) void k_ep_late(Params p, int after_reset) {
   Core<WaveGfx950, 1>::ep_log_late(p, (int)blockIdx.x, after_reset != 0);
 }
 
+// sf_replay_step's two small launches around the halves of an iteration (sf_core.hpp replay_fetch): mode 0 the loop-top
+// check and the line of `ind`, mode 1 the lines of the other commanded humans.  One wavefront per arena and workgroup.
+__global__ __launch_bounds__(64) void k_replay_fetch(Params p, Replay r, int mode) {
+  Core<WaveGfx950, 1>::replay_fetch(p, r, (int)blockIdx.x, mode);
+}
+
 // Episode log collection (sf_episodes_device): two launches, no host round trip, so that the pair can sit in a captured
 // graph behind the step launches.
 // k_ep_plan: one 1024-thread workgroup, thread t owns a contiguous run of arenas.  Per arena pending = episodes - cursor,
@@ -1102,6 +1108,12 @@ struct HipRT {
     SF_HIP(hipGetLastError());
     return SF_OK;
   }
+  int launch_replay_fetch(const Params &p, const Replay &r, int mode) {
+    SF_HIP(hipSetDevice(device));
+    hipLaunchKernelGGL(k_replay_fetch, dim3((unsigned)p.A), dim3(64), 0, stream, p, r, mode);
+    SF_HIP(hipGetLastError());
+    return SF_OK;
+  }
   int launch_episodes(const Params &p, const uint32_t *ring, int depth, int32_t *cursor, int32_t *plan, int32_t *out,
                       int max_records, int32_t *counts) {
     SF_HIP(hipSetDevice(device));
@@ -1345,6 +1357,26 @@ int sf_episodes_device(sf_env *env, int32_t *d_out, int32_t max_records, int32_t
 int sf_episode_ring(sf_env *env, int32_t *out_host) {
   SF_ENV(env);
   return env->e.episode_ring_host(out_host);
+}
+int sf_replay_load(sf_env *env, const uint8_t *streams, const int64_t *offsets) {
+  SF_ENV(env);
+  return env->e.replay_load(streams, offsets);
+}
+int sf_replay_step(sf_env *env) {
+  SF_ENV(env);
+  return env->e.replay_step();
+}
+int sf_replay_status(sf_env *env, int32_t *out_host) {
+  SF_ENV(env);
+  return env->e.replay_status_host(out_host);
+}
+int sf_replay_status_device(sf_env *env, int32_t *d_out) {
+  SF_ENV(env);
+  return env->e.replay_status_device(d_out);
+}
+int sf_replay_commands_device(sf_env *env, uint8_t *d_out) {
+  SF_ENV(env);
+  return env->e.replay_commands_device(d_out);
 }
 int sf_done_device(sf_env *env, uint8_t *d_out) {
   SF_ENV(env);

@@ -1806,6 +1806,66 @@ struct Core {
     }
   }
 
+  // k_replay_fetch (sf_replay_step): the replay_mode reads of the reference, `replay_file >> command[ind]` (G:968-969) and
+  // `replay_file >> command[i]` for every other human with mh[i] && remote[i] (G:979-986), done where the state is.  One
+  // wavefront per arena, lane g = commanded human g.
+  // mode 0, in front of the iteration's first half = the loop top as the replay sees it: an arena that is still replaying
+  // and whose game check_end has not ended (G:1450) either finds its stream empty and stops — SC_DONE = 1, SC_OUTCOME =
+  // SF_SAMPLE_END, nothing else: Core::step returns at once for a done arena, so it stands still like a finished game, but
+  // no episode is counted, latched or logged — or takes the line of `ind`.  An arena whose stream was cut in the middle of
+  // the iteration before (state truncated) stops here too.
+  // mode 1, between the halves: lane g != ind takes a line iff its human is alive and still commanded (k_agent_alive's
+  // predicate; a dead player's slot handed to a spawned NPC takes none), its line being the rank of its lane in the
+  // ballot of those lanes, counted from the cursor.  Lanes whose line lies behind the end of the stream keep '+' (what a
+  // failed `replay_file >> command[i]` leaves, G:1009) and the arena is marked truncated.
+  // The cursor and the status words are written by lane 0 with vector stores.
+  static SF_DEV void replay_fetch(const Params &p, const Replay &r, int a, int mode) {
+    int32_t *const st = r.status + (size_t)a * RP_WORDS;
+    int32_t *const sc = p.scal + (size_t)a * SC_WORDS;
+    const int32_t state = W::uload_i32(st + RP_STATE);
+    const uint32_t cur = (uint32_t)W::uload_i32(st + RP_CURSOR);
+    const uint32_t o0 = (uint32_t)W::uload_i32((const int32_t *)r.off + a), o1 = (uint32_t)W::uload_i32((const int32_t *)r.off + a + 1);
+    const uint32_t len = o1 - o0;
+    const int32_t done = W::uload_i32(sc + SC_DONE);
+    const P ag = W::ltu(W::lane(), (uint32_t)p.n_agents);
+    const V row = W::lane() + (uint32_t)a * (uint32_t)p.n_agents;
+    const P me = W::lane() == (uint32_t)p.ind;
+    if (mode == 0) {
+      bool go = false;
+      if (state == SF_REPLAY_RUNNING && done) {
+        W::ustore_i32(st + RP_STATE, SF_REPLAY_GAME_ENDED);
+      } else if ((state == SF_REPLAY_RUNNING || state == SF_REPLAY_TRUNCATED) && !done) {
+        if (state == SF_REPLAY_TRUNCATED || cur == len) {
+          W::ustore_i32(sc + SC_DONE, 1), W::ustore_i32(sc + SC_OUTCOME, SF_SAMPLE_END);
+          if (state == SF_REPLAY_RUNNING) W::ustore_i32(st + RP_STATE, SF_REPLAY_SAMPLE_ENDED);
+        } else {
+          go = true;
+        }
+      }
+      const P first = go ? me : W::frombits(0ull);  // the lane of `ind`, where the arena goes on
+      const V tok = W::gload_u8(r.streams, V(o0 + cur), first);
+      W::gstore_u8(r.cmd, row, W::select(first, tok, V((uint32_t)'+')), ag);
+      W::gstore_u8(r.taken, row, tok, ag);  // (0 on every lane that loaded nothing)
+      if (go) {
+        W::ustore_i32(st + RP_CURSOR, (int32_t)(cur + 1u));
+        W::ustore_i32(st + RP_ITER, W::uload_i32(st + RP_ITER) + 1);
+      }
+      return;
+    }
+    if (state != SF_REPLAY_RUNNING || done) return;  // only an arena that took the line of `ind` at this loop top
+    const V fl = W::gload(p.hum, W::lane() + ((uint32_t)HW_FLAGS * (uint32_t)p.A + (uint32_t)a) * (uint32_t)p.H, ag);
+    const P takes = ag & !me & ((fl & (HF_ALIVE | HF_CTRL)) == (HF_ALIVE | HF_CTRL));
+    const uint64_t bal = W::ballot(takes);
+    const V line = V(cur) + W::rank_below(bal);
+    const P have = takes & W::ltu(line, V(len));
+    const V tok = W::gload_u8(r.streams, line + o0, have);
+    W::gstore_u8(r.cmd, row, tok, have);
+    W::gstore_u8(r.taken, row, tok, have);
+    const uint32_t want = (uint32_t)W::popc64(bal), left = len - cur, got = want < left ? want : left;
+    W::ustore_i32(st + RP_CURSOR, (int32_t)(cur + got));
+    if (got < want) W::ustore_i32(st + RP_STATE, SF_REPLAY_TRUNCATED);
+  }
+
   // top of play()'s while(true): G:1444-1450
   template <bool LOG = false>
   static SF_DEV void loop_top(Arena &S, uint8_t *lds, const Params &p, int a) {

@@ -210,6 +210,9 @@ struct Env {
   // the collection's plan [3][A] (first output record, records delivered, first episode delivered); sf_episodes' staging
   int32_t *d_ep_cursor = nullptr, *d_ep_plan = nullptr, *d_ep_out = nullptr, *d_ep_counts = nullptr;
   size_t ep_out_records = 0;
+  // command streams of logged games (sf_replay_load): rp.cmd is d_cmd; everything else is allocated by the load and
+  // freed by sf_replay_load(NULL, NULL).  Null while nothing is loaded
+  Replay rp = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int balance = 1;             // SF_BALANCE=0 switches the ordering off (A/B measurements)
   int rank_k_min = 8;          // launches of fewer steps run in arena order
   int rank_every = 100;        // steps between two orderings (SF_RANK_EVERY; measured: tools/experiments/README.md)
@@ -375,7 +378,7 @@ struct Env {
   void destroy() {
     void *ptrs[] = {d_logt, d_exptab, d_tab, d_map_flags, d_map_pidx, d_map_exits, p.hum, p.zom, p.bul, p.por, p.rng, p.rng2, p.scal, p.results,
                     p.flags, p.aux_dmg, p.aux_pidx, d_tb, d_serial, d_cmd, d_obs, d_nzprev, d_perm, tab.ep_ring, d_ep_cursor,
-                    d_ep_plan, d_ep_out, d_ep_counts};
+                    d_ep_plan, d_ep_out, d_ep_counts, (void *)rp.streams, (void *)rp.off, rp.status, rp.taken};
     for (void *q : ptrs)
       if (q) rt.free(q);
     rt.shutdown();
@@ -387,6 +390,7 @@ struct Env {
     rt.h2d(d_serial, serial, sizeof(uint64_t) * (size_t)p.A);
     rt.zero(p.results, (size_t)p.A * p.n_agents * 8 * sizeof(int32_t));
     if (tab.ep_ring) rt.zero(d_ep_cursor, (size_t)p.A * sizeof(int32_t));  // (k_ep_late empties the rings)
+    if (rp.status) replay_rewind();
     int rc = rt.launch_reset(p, NB, d_tb, d_serial);
     if (rc || (rc = ep_late(true))) return rc;
     was_reset = true;
@@ -447,6 +451,85 @@ struct Env {
     rt.h2d(d_cmd, cmd, (size_t)p.A * p.n_agents);
     return step_end_device(d_cmd);
   }
+  // ---- replay of logged games: per-arena command streams fetched on the device (sf_replay_load / sf_replay_step) ----
+  void replay_free() {
+    void *old[] = {(void *)rp.streams, (void *)rp.off, rp.status, rp.taken};
+    for (void *q : old)
+      if (q) rt.free(q);
+    rp = Replay{nullptr, nullptr, nullptr, nullptr, nullptr};
+  }
+  void replay_rewind() {  // every stream from its first line again, nothing taken yet
+    rt.zero(rp.status, (size_t)p.A * RP_WORDS * sizeof(int32_t));
+    rt.zero(rp.taken, (size_t)p.A * p.n_agents);
+  }
+  int replay_load(const uint8_t *streams, const int64_t *offsets) {
+    if (int rc = not_mid_step("sf_replay_load")) return rc;
+    int rc = rt.sync();  // launches still in flight may read the old streams
+    if (rc) return rc;
+    if (!streams && !offsets) {
+      replay_free();
+      return SF_OK;
+    }
+    if (!offsets) return fail(SF_ERR_ARG, "sf_replay_load: null offsets");
+    if (p.auto_reset) return fail(SF_ERR_STATE, "sf_replay_load: a replay needs auto_reset == 0 (a logged game is one episode)");
+    const size_t A = (size_t)p.A;
+    if (offsets[0] < 0) return fail(SF_ERR_ARG, "sf_replay_load: negative offset");
+    for (size_t a = 0; a < A; ++a)
+      if (offsets[a + 1] < offsets[a]) return fail(SF_ERR_ARG, "sf_replay_load: offsets must not decrease");
+    const int64_t total = offsets[A] - offsets[0];
+    if (total >= ((int64_t)1 << 32)) return fail(SF_ERR_ARG, "sf_replay_load: 4 GiB of commands or more in one load");
+    if (total > 0 && !streams) return fail(SF_ERR_ARG, "sf_replay_load: null streams");
+    replay_free();
+    std::vector<uint32_t> off(A + 1);
+    for (size_t a = 0; a <= A; ++a) off[a] = (uint32_t)(offsets[a] - offsets[0]);
+    uint8_t *d_streams = nullptr;
+    uint32_t *d_off = nullptr;
+    if ((rc = alloc(d_streams, (size_t)total)) || (rc = alloc(d_off, A + 1)) || (rc = alloc(rp.status, A * RP_WORDS)) ||
+        (rc = alloc(rp.taken, A * p.n_agents))) {
+      rp.streams = d_streams, rp.off = d_off;
+      replay_free();
+      return rc;
+    }
+    rp.streams = d_streams, rp.off = d_off, rp.cmd = d_cmd;
+    if (total > 0) rt.h2d(d_streams, streams + offsets[0], (size_t)total);
+    rt.h2d(d_off, off.data(), (A + 1) * sizeof(uint32_t));
+    replay_rewind();
+    return rt.sync();  // (the staging vector and the caller's buffer are free again)
+  }
+  int replay_loaded(const char *what) const {
+    return rp.status ? SF_OK : fail(SF_ERR_STATE, std::string(what) + ": no command streams loaded (sf_replay_load)");
+  }
+  // one iteration of every arena, the commands taken from the streams on the device: loop-top check -> first half ->
+  // fetch -> second half (+ k_ep_late where sf_step_end launches it); no host synchronisation
+  int replay_step() {
+    if (int rc = replay_loaded("sf_replay_step")) return rc;
+    if (!was_reset) return fail(SF_ERR_STATE, "sf_replay_step before sf_reset");
+    if (int rc = not_mid_step("sf_replay_step")) return rc;
+    int rc;
+    if ((rc = rt.launch_replay_fetch(p, rp, 0)) || (rc = rt.launch_step_half(p, NB, d_cmd, 1))) return rc;
+    if (p.n_agents > 1 && (rc = rt.launch_replay_fetch(p, rp, 1))) return rc;  // (a lone player has no other lines)
+    if ((rc = rt.launch_step_half(p, NB, d_cmd, 2))) return rc;
+    return ep_late(false);
+  }
+  int replay_status_host(int32_t *out) {
+    if (!out) return fail(SF_ERR_ARG, "null output buffer");
+    if (int rc = replay_loaded("sf_replay_status")) return rc;
+    rt.d2h(out, rp.status, (size_t)p.A * RP_WORDS * sizeof(int32_t));
+    return rt.sync();
+  }
+  int replay_status_device(int32_t *d_out) {
+    if (!d_out) return fail(SF_ERR_ARG, "null output buffer");
+    if (int rc = replay_loaded("sf_replay_status_device")) return rc;
+    rt.d2d(d_out, rp.status, (size_t)p.A * RP_WORDS * sizeof(int32_t));
+    return SF_OK;
+  }
+  int replay_commands_device(uint8_t *d_out) {
+    if (!d_out) return fail(SF_ERR_ARG, "null output buffer");
+    if (int rc = replay_loaded("sf_replay_commands_device")) return rc;
+    rt.d2d(d_out, rp.taken, (size_t)p.A * p.n_agents);
+    return SF_OK;
+  }
+
   int agent_alive_device(uint8_t *d_out) {
     if (!d_out) return fail(SF_ERR_ARG, "null output buffer");
     if (!was_reset) return fail(SF_ERR_STATE, "sf_agent_alive before sf_reset");

@@ -114,6 +114,20 @@ struct Tables {
 constexpr int EP_HDR_WORDS = 8;
 SF_HD inline int ep_record_words(int n_agents) { return EP_HDR_WORDS + 8 * n_agents; }
 
+// ---- command streams of logged games (sf_replay_load, sf_core.hpp replay_fetch) ---------------------------------
+// One stream of reference command chars per arena, in the order the reference's human_action logs them
+// (gameplay.hpp:966-967,982-983): per iteration the command of `ind`, then one for every other commanded human that is
+// alive and remote at that moment, slots ascending.  A struct of its own, passed to k_replay_fetch only: Params, and with
+// it every step kernel's argument offsets and register allocation, stays as it is.
+enum { RP_STATE = 0, RP_CURSOR, RP_ITER, RP_PAD, RP_WORDS };  // the status words sf_replay_status hands out
+struct Replay {
+  const uint8_t *streams;  // all streams back to back
+  const uint32_t *off;     // [A + 1]: arena a owns streams[off[a] .. off[a + 1])
+  int32_t *status;         // [A][RP_WORDS]: SF_REPLAY_* state, cursor (tokens taken), iterations played, 0
+  uint8_t *cmd;            // [A][n_agents]: the command row k_step_half's second phase reads ('+' where no line was taken)
+  uint8_t *taken;          // [A][n_agents]: the line each commanded human took in the last iteration, 0 where none
+};
+
 // ---- everything a kernel needs -----------------------------------------------------------------------
 struct Params {
   int32_t A, F, N, M, cells, cells_pad;

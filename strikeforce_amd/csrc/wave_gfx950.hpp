@@ -333,6 +333,13 @@ struct WaveGfx950 {
   static SF_DEV void gstore(uint32_t *base, V idx, V val, P pred) {
     if (pred) gptr(base)[idx] = val;
   }
+  static SF_DEV void gstore_u8(uint8_t *base, V idx, V val, P pred) {
+    if (pred) gptr(base)[idx] = (uint8_t)val;
+  }
+  // set bits of a ballot below this lane (v_mbcnt_lo / v_mbcnt_hi): the lane's rank among the lanes that voted
+  static SF_DEV V rank_below(uint64_t bal) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+  }
 
   // flag plane <-> LDS, 16 B per lane per pass (nbytes is a multiple of 16)
   // (four loads in flight before the first LDS store: written one by one, each copy waited for its own load —

@@ -61,6 +61,14 @@ def load_library():
             L.sf_episodes_allgather.argtypes = [vp, vp]
             for n in ("sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather"):
                 getattr(L, n).restype = C.c_int
+        if hasattr(L, "sf_replay_load"):  # (replay of logged games; an older build loaded through SF_LIBRARY_PATH lacks it)
+            L.sf_replay_load.argtypes = [vp, vp, vp]
+            L.sf_replay_step.argtypes = [vp]
+            L.sf_replay_status.argtypes = [vp, vp]
+            L.sf_replay_status_device.argtypes = [vp, vp]
+            L.sf_replay_commands_device.argtypes = [vp, vp]
+            for n in REPLAY_EXPORTS:
+                getattr(L, n).restype = C.c_int
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -84,13 +92,17 @@ def load_library():
     return _LIB
 
 
+REPLAY_EXPORTS = ("sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device",
+                  "sf_replay_commands_device")
+
 # every symbol include/strikeforce.h declares
 EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step", "sf_step_device", "sf_observe",
            "sf_observe_device", "sf_observe_device_delta", "sf_observe_sparse_device", "sf_observe_overflow_device", "sf_results", "sf_results_device", "sf_done", "sf_done_device", "sf_done_view_device", "sf_state_digest", "sf_dump_arena",
            "sf_set_stream", "sf_synchronize", "sf_kernel_time", "sf_last_error", "sf_abi_version",
            "sf_comm_unique_id", "sf_comm_init", "sf_results_allgather", "sf_comm_wait", "sf_comm_ranks",
            "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
-           "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather"]
+           "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
+           "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device"]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -301,6 +313,49 @@ class ArenaBatch:
         """RCCL all-gather of every rank's raw rings into [world][arenas][depth][record words] int32, on a side stream."""
         self._need_log()
         self._ck(self.L.sf_episodes_allgather(self.h, C.c_void_p(d_out_ptr)), "sf_episodes_allgather")
+
+    # ---- replay of logged games (strikeforce.h sf_replay_load) ----
+    def _need_replay(self):
+        if not hasattr(self.L, "sf_replay_load"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_replay_* entry points")
+
+    def replay_load(self, streams):
+        """One command stream per arena — str / bytes of reference command chars in file order, or objects with a
+        `.commands` attribute (replay.Sample) — uploaded to the device, every cursor at its stream's start.  None frees
+        them.  Needs auto_reset == 0; the seeds are reset()'s."""
+        self._need_replay()
+        if streams is None:
+            self._ck(self.L.sf_replay_load(self.h, None, None), "sf_replay_load")
+            return
+        rows = [getattr(s, "commands", s) for s in streams]
+        rows = [r.encode("ascii") if isinstance(r, str) else bytes(r) for r in rows]
+        if len(rows) != self.cfg.arenas:
+            raise ValueError("replay_load takes one command stream per arena")
+        off = np.zeros(len(rows) + 1, dtype=np.int64)
+        off[1:] = np.cumsum([len(r) for r in rows])
+        flat = np.frombuffer(b"".join(rows) or b"\0", dtype=np.uint8)
+        self._ck(self.L.sf_replay_load(self.h, C.c_void_p(flat.ctypes.data), C.c_void_p(off.ctypes.data)), "sf_replay_load")
+
+    def replay_step(self):
+        """One iteration of every arena, the commands fetched from the loaded streams on the device (no host round trip)."""
+        self._need_replay()
+        self._ck(self.L.sf_replay_step(self.h), "sf_replay_step")
+
+    def replay_status(self):
+        """int32 [arenas][4]: state (abi.REPLAY_*), cursor (lines taken), iterations played, 0."""
+        self._need_replay()
+        out = np.zeros((self.cfg.arenas, 4), dtype=np.int32)
+        self._ck(self.L.sf_replay_status(self.h, C.c_void_p(out.ctypes.data)), "sf_replay_status")
+        return out
+
+    def replay_status_device(self, d_out_ptr):
+        self._need_replay()
+        self._ck(self.L.sf_replay_status_device(self.h, C.c_void_p(d_out_ptr)), "sf_replay_status_device")
+
+    def replay_commands_device(self, d_out_ptr):
+        """uint8 [arenas][n_agents] on the device: the line each commanded human took in the last iteration, 0 where none."""
+        self._need_replay()
+        self._ck(self.L.sf_replay_commands_device(self.h, C.c_void_p(d_out_ptr)), "sf_replay_commands_device")
 
     def done_device(self, d_out_ptr):
         """check_end()'s verdict on the device, one byte per (arena, agent): what PolicyBatch.reset_memory takes."""
