@@ -220,10 +220,31 @@ static inline size_t obs_lds_bytes(const Params &p) {
   return (size_t)(HW_WORDS * p.H + (p.Z <= OBS_Z_STAGE ? ZW_WORDS * p.Z : 0) + BW_WORDS * p.B) * sizeof(uint32_t) + sizeof(int32_t) * 12 +
          sizeof(Derived) * (size_t)(p.npc_block + 1);
 }
+// The observation kernels' limits can be set from the compiler's command line (-DSF_OBS_REC_MAX=24 ...): a test build with
+// small limits makes ordinary worlds take every fallback below (tests/obs_flavour.py).  The defaults are the product's.
+#ifndef SF_OBS_REC_MAX
+#define SF_OBS_REC_MAX 72
+#endif
+#ifndef SF_OBS_LIST_MAX
+#define SF_OBS_LIST_MAX 256
+#endif
+#ifndef SF_OBS_STAGED
+#define SF_OBS_STAGED (2 * OBS_W2)
+#endif
+#ifndef SF_OL_REC
+#define SF_OL_REC 48
+#endif
+#ifndef SF_OL_POWQ
+#define SF_OL_POWQ 384
+#endif
+#ifndef SF_OL_CELLS
+#define SF_OL_CELLS 640
+#endif
 constexpr int OBS_CLASS_RECS = 8;   // shared records of plain static cells: '#', '^', 'v', 'O', chest types 0-3
-constexpr int OBS_REC_MAX = 72;     // + cells with an entity or a player-built object on them (own record each)
-constexpr int OBS_LIST_MAX = 256;  // (a) values that need a real pow, (b) overflow cells' outputs
+constexpr int OBS_REC_MAX = SF_OBS_REC_MAX;     // + cells with an entity or a player-built object on them (own record each)
+constexpr int OBS_LIST_MAX = SF_OBS_LIST_MAX;  // (a) values that need a real pow, (b) overflow cells' outputs
 constexpr uint32_t OBS_NOREC = 255u;
+static_assert(OBS_REC_MAX > OBS_CLASS_RECS && OBS_REC_MAX <= (int)OBS_NOREC && OBS_LIST_MAX >= 1, "a record slot is one byte, 255 = none");
 
 // One workgroup per (arena, agent).  The 123 KB observation is written exactly once, with 16-B-per-lane stores
 // that cover whole 128-B lines (scattered 4-byte stores of the few non-zero values cost more HBM time than the
@@ -509,7 +530,8 @@ static __device__ __forceinline__ void observe_agent(const Params &p, float *out
     // own bits into entries would make the others wait for the fullest words (13 k of the kernel's 42 k cycles).  The
     // threads only drop their bits' dense indices into an LDS list (occ[] and wdmg[] are dead by now), and the entries
     // are then built and stored round-robin: equal work, coalesced stores.
-    constexpr uint32_t STAGED = 2u * (uint32_t)OBS_W2;
+    constexpr uint32_t STAGED = (uint32_t)(SF_OBS_STAGED);
+    static_assert(STAGED <= 2u * (uint32_t)OBS_W2, "the staging area is occ[] and wdmg[]");
     if (total <= STAGED) {
       uint32_t *stage0 = occ, *stage1 = reinterpret_cast<uint32_t *>(wdmg);
 #pragma unroll
@@ -628,12 +650,13 @@ __global__ __launch_bounds__(OBS_THREADS) void k_observe_redo(Params p, float *o
 // with the dense observation float by float).  A window with more than OL_REC own records is "crowded" (count
 // 0xffffffff: the caller takes the dense call for that agent, as before; the dense kernel's own limit is 64).
 // LDS: 9.7 KB per wavefront, so that the 16 wavefronts a CU gets of a 4096-agent launch are resident together.
-constexpr int OL_REC = 48;                            // own records per window
+constexpr int OL_REC = SF_OL_REC;                            // own records per window
 constexpr int OL_STRIDE = SF_OBS_CHANNELS + 1;        // (odd stride: the lanes of pass 2b write different banks)
 constexpr int OL_PASSES = (OBS_W2 + 63) / 64;         // 16
-constexpr int OL_POWQ = 384;                          // queued x^(1/5) evaluations per window; more are done in place
-constexpr int OL_CELLS = 640;                         // non-empty cells per window (walls included); more: "crowded"
+constexpr int OL_POWQ = SF_OL_POWQ;                          // queued x^(1/5) evaluations per window; more are done in place
+constexpr int OL_CELLS = SF_OL_CELLS;                         // non-empty cells per window (walls included); more: "crowded"
 static_assert(OL_REC + OBS_CLASS_RECS <= 64 && OBS_W2 <= 1024, "a compact cell entry is window cell | slot << 10 in 16 bits");
+static_assert(OL_CELLS % 64 == 0 && OL_CELLS >= 64 && OL_POWQ >= 1, "the compact cells leave in whole passes of 64");
 // LDS of one window, carved out of a caller-provided region (the stand-alone kernel's own, or k_step's dynamic region
 // once the step has stored its state): 16-byte aligned, OL_LDS_BYTES long
 struct ObsListLds {
@@ -807,7 +830,8 @@ static __device__ __forceinline__ void observe_list_wave(const Params &p, const 
       if (q < (uint32_t)OL_POWQ)
         L.powq[q] = (uint16_t)(l * OL_STRIDE + k);
       else
-        rec[l * OL_STRIDE + k] = obs_map(x);  // (obs_map of a table entry is the table's value up to the host's libm: never reached in practice)
+        rec[l * OL_STRIDE + k] = obs_map(x);  // (obs_map of a table entry is the table's value up to the host's libm; no game reaches this
+                                              // at 384, the small-limits test build does and gets the dense kernel's bits, tests/test_gpu_obs_edges.py)
     });
     L.recmask[l] = m;
   }

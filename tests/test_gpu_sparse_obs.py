@@ -152,14 +152,22 @@ def test_a_list_capacity_above_the_kernels_limit_is_refused(cnn):
 def test_crowded_windows_are_marked_not_truncated():
     """MAXCAP (64 humans, 64 zombies, 256 bullet slots on 48 x 48): windows with more occupied cells than the kernel has
     records take the dense call's slow path; the list form must say so (count 0xffffffff) instead of handing over a partial
-    list, and every other agent's list must still equal its dense observation."""
+    list, and every other agent's list must still equal its dense observation.  An agent is marked if and only if the
+    oracle's own state says its window has more than 48 own-record cells or more than 640 non-empty ones
+    (tests/obs_cases.py), so no agent escapes the comparison on any other ground."""
+    import obs_cases
+    import obs_flavour
     w = config.baseline_workload("MAXCAP", arenas=4)
-    g = env.ArenaBatch(w)
-    g.reset(*w.seeds())
+    o, g = Oracle(w), env.ArenaBatch(w)
+    tb, sr = w.seeds()
+    o.reset(tb, sr), g.reset(tb, sr)
     B = w.cfg.arenas * w.cfg.n_agents
     marked = 0
     for _ in range(6):
         _advance(w, g, 40)
+        o.step_many(config.bench_commands(w.cfg.arenas, w.cfg.n_agents, 40)[0])
+        assert (o.digest() == g.digest()).all()
+        must = obs_cases.marked(obs_cases.window_stats(o), obs_flavour.PRODUCT).reshape(-1)
         d_obs = torch.zeros((B, 32, 31, 31), dtype=torch.float32, device="cuda")
         keys, vals, counts, pov = _bufs(B)
         g.observe_device(d_obs.data_ptr())
@@ -169,6 +177,7 @@ def test_crowded_windows_are_marked_not_truncated():
         k, v, n = keys.cpu().numpy().view(np.uint32), vals.cpu().numpy(), counts.cpu().numpy().view(np.uint32)
         for a in range(B):
             nz = np.flatnonzero(obs[a])
+            assert (n[a] == 0xFFFFFFFF) == bool(must[a]), "agent %d: count %d, the oracle says marked = %s" % (a, n[a], must[a])
             if n[a] == 0xFFFFFFFF:
                 marked += 1
                 continue
@@ -178,7 +187,7 @@ def test_crowded_windows_are_marked_not_truncated():
             y, x = np.divmod(r, 31)
             assert np.array_equal(k[a, :m], (ch * 9) | (y << 9) | (x << 14))
             assert np.array_equal(v[a, :m].view(np.uint32), obs[a][nz[:m]].view(np.uint32))
-    print("agents marked as crowded:", marked)
+    assert marked > 0  # (30 of these 353 live windows, by the oracle)
 
 
 @pytest.mark.parametrize("which,cap,arenas", [("C2", 16, 8), ("C3", 200, 24), ("MAXCAP", 2048, 4)])
