@@ -2,7 +2,7 @@
 // as pure per-element functions over the HBM arena state: for one (arena, agent) the 31x31 window around
 // the agent's human is described by 32 channels, channel-major, each mapped by x -> (float)pow(|x|/10, 0.2).
 //
-// The kernel in sf_api.hip stages, per window cell, the flag byte and an occupant word
+// The kernel in sf_obs_kernels.hpp stages, per window cell, the flag byte and an occupant word
 // (human+1 | (zombie+1) << OCC_Z_SH | (designated bullet+1) << OCC_B_SH) in LDS and then evaluates obs_value() for
 // every one of the 30 752 outputs with coalesced stores.  tests/emu calls the same functions in loops.
 #pragma once

@@ -202,4 +202,30 @@ inline size_t lds_bytes_for(int cells_pad, int lds_tab, int Z, int P) {
 constexpr int LDS_PLANE_MAX = 12 * 1024;
 inline bool hbm_plane(int cells_pad) { return cells_pad > LDS_PLANE_MAX; }
 
+// The instances of the per-arena kernels (k_reset, k_step, k_step_half; Core<W, NB, HP, BM, ZL>) and the one a configuration
+// runs.  Built: NB 1..4 x {(HP 0, BM 1), (HP 1, BM 1), (HP 1, BM 0)}, and the same three with ZL (large pools) for NB 4 —
+// 15.  Host code; every runtime (sf_api.hip HipRT, the tests' CPU runtime) selects through with_variant.
+template <int NB_, bool HP_, bool BM_, bool ZL_>
+struct KernelVariant {
+  static constexpr int NB = NB_;
+  static constexpr bool HP = HP_, BM = BM_, ZL = ZL_;
+};
+template <int NB, bool ZL, class F>
+int with_plane_variant(const Params &p, F &&f) {
+  if (!hbm_plane(p.cells_pad)) return f(KernelVariant<NB, false, true, ZL>{});
+  if (use_bitmaps(p.cells_pad)) return f(KernelVariant<NB, true, true, ZL>{});
+  return f(KernelVariant<NB, true, false, ZL>{});
+}
+// f(KernelVariant<..>{}) for the instance of configuration `p` with NB bullet words (Env::create: 4 with large pools); returns f's int
+template <class F>
+int with_variant(const Params &p, int NB, F &&f) {
+  if (large_pools(p.Z, p.P)) return with_plane_variant<4, true>(p, f);
+  switch (NB) {
+    case 1: return with_plane_variant<1, false>(p, f);
+    case 2: return with_plane_variant<2, false>(p, f);
+    case 3: return with_plane_variant<3, false>(p, f);
+    default: return with_plane_variant<4, false>(p, f);
+  }
+}
+
 }  // namespace sf

@@ -21,48 +21,17 @@ enum { LV_RESET = 0, LV_STEP, LV_STEP_HALF, LV_KINDS };
 struct Variant {
   int32_t nb = 0, hp = 0, bm = 0, zl = 0;
 };
-template <int NB, bool HP, bool BM, bool ZL>
-static void note(Variant &v) {
-  v.nb = NB, v.hp = HP, v.bm = BM, v.zl = ZL;
-}
 
-// same variant choice as the HIP launchers: big flag planes stay in "HBM" (here: the host arrays)
-template <int NB, bool ZL>
-static void run_reset(const Params &p, const uint64_t *tb, const uint64_t *serial, Variant &v) {
+// One emulated launch of a per-arena kernel.  The instance is the one the product's own selector picks (sf_types.hpp
+// with_variant; big flag planes stay in "HBM", here the host arrays); noted in `last`, then fn(lds, arena) for every arena.
+template <class V>
+using EmuCore = Core<WaveEmu, V::NB, V::HP, V::BM, V::ZL>;
+template <class V, class F>
+static int each_arena(const Params &p, Variant &last, V, F fn) {
+  last = {V::NB, V::HP, V::BM, V::ZL};
   std::vector<uint8_t> lds(lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P));
-  for (int a = 0; a < p.A; ++a) {
-    if (!hbm_plane(p.cells_pad))
-      Core<WaveEmu, NB, false, true, ZL>::reset_body(lds.data(), p, a, tb, serial), note<NB, false, true, ZL>(v);
-    else if (use_bitmaps(p.cells_pad))
-      Core<WaveEmu, NB, true, true, ZL>::reset_body(lds.data(), p, a, tb, serial), note<NB, true, true, ZL>(v);
-    else
-      Core<WaveEmu, NB, true, false, ZL>::reset_body(lds.data(), p, a, tb, serial), note<NB, true, false, ZL>(v);
-  }
-}
-template <int NB, bool ZL>
-static void run_step(const Params &p, const uint8_t *cmds, int k, Variant &v) {
-  std::vector<uint8_t> lds(lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P));
-  for (int a = 0; a < p.A; ++a) {
-    if (!hbm_plane(p.cells_pad))
-      Core<WaveEmu, NB, false, true, ZL>::step_body(lds.data(), p, a, cmds, k), note<NB, false, true, ZL>(v);
-    else if (use_bitmaps(p.cells_pad))
-      Core<WaveEmu, NB, true, true, ZL>::step_body(lds.data(), p, a, cmds, k), note<NB, true, true, ZL>(v);
-    else
-      Core<WaveEmu, NB, true, false, ZL>::step_body(lds.data(), p, a, cmds, k), note<NB, true, false, ZL>(v);
-  }
-}
-
-template <int NB, bool ZL>
-static void run_step_half(const Params &p, const uint8_t *cmds, int phase, Variant &v) {
-  std::vector<uint8_t> lds(lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P));
-  for (int a = 0; a < p.A; ++a) {
-    if (!hbm_plane(p.cells_pad))
-      Core<WaveEmu, NB, false, true, ZL>::step_half_body(lds.data(), p, a, cmds, phase), note<NB, false, true, ZL>(v);
-    else if (use_bitmaps(p.cells_pad))
-      Core<WaveEmu, NB, true, true, ZL>::step_half_body(lds.data(), p, a, cmds, phase), note<NB, true, true, ZL>(v);
-    else
-      Core<WaveEmu, NB, true, false, ZL>::step_half_body(lds.data(), p, a, cmds, phase), note<NB, true, false, ZL>(v);
-  }
+  for (int a = 0; a < p.A; ++a) fn(lds.data(), a);
+  return SF_OK;
 }
 
 static void run_observe(const Params &p, float *out) {
@@ -128,45 +97,21 @@ struct CpuRT {
   void zero(void *d, size_t n) { memset(d, 0, n); }
   int sync() { return SF_OK; }
   int launch_reset(const Params &p, int NB, const uint64_t *tb, const uint64_t *serial) {
-    if (large_pools(p.Z, p.P)) {
-      run_reset<4, true>(p, tb, serial, last[LV_RESET]);
-      return SF_OK;
-    }
-    switch (NB) {
-      case 1: run_reset<1, false>(p, tb, serial, last[LV_RESET]); break;
-      case 2: run_reset<2, false>(p, tb, serial, last[LV_RESET]); break;
-      case 3: run_reset<3, false>(p, tb, serial, last[LV_RESET]); break;
-      default: run_reset<4, false>(p, tb, serial, last[LV_RESET]); break;
-    }
-    return SF_OK;
+    return with_variant(p, NB, [&](auto v) {
+      return each_arena(p, last[LV_RESET], v, [&](uint8_t *lds, int a) { EmuCore<decltype(v)>::reset_body(lds, p, a, tb, serial); });
+    });
   }
   int launch_step(const Params &p, int NB, const uint8_t *cmds, int k) {
-    if (large_pools(p.Z, p.P)) {
-      run_step<4, true>(p, cmds, k, last[LV_STEP]);
-      return SF_OK;
-    }
-    switch (NB) {
-      case 1: run_step<1, false>(p, cmds, k, last[LV_STEP]); break;
-      case 2: run_step<2, false>(p, cmds, k, last[LV_STEP]); break;
-      case 3: run_step<3, false>(p, cmds, k, last[LV_STEP]); break;
-      default: run_step<4, false>(p, cmds, k, last[LV_STEP]); break;
-    }
-    return SF_OK;
+    return with_variant(p, NB, [&](auto v) {
+      return each_arena(p, last[LV_STEP], v, [&](uint8_t *lds, int a) { EmuCore<decltype(v)>::step_body(lds, p, a, cmds, k); });
+    });
   }
   bool can_rank() const { return false; }  // (a launch order only matters where arenas run side by side)
   int launch_rank(const Params &, uint32_t *) { return SF_OK; }
   int launch_step_half(const Params &p, int NB, const uint8_t *cmds, int phase) {
-    if (large_pools(p.Z, p.P)) {
-      run_step_half<4, true>(p, cmds, phase, last[LV_STEP_HALF]);
-      return SF_OK;
-    }
-    switch (NB) {
-      case 1: run_step_half<1, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
-      case 2: run_step_half<2, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
-      case 3: run_step_half<3, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
-      default: run_step_half<4, false>(p, cmds, phase, last[LV_STEP_HALF]); break;
-    }
-    return SF_OK;
+    return with_variant(p, NB, [&](auto v) {
+      return each_arena(p, last[LV_STEP_HALF], v, [&](uint8_t *lds, int a) { EmuCore<decltype(v)>::step_half_body(lds, p, a, cmds, phase); });
+    });
   }
   int launch_agent_alive(const Params &p, uint8_t *out) {
     for (int i = 0; i < p.A * p.n_agents; ++i) {

@@ -1,5 +1,5 @@
 """Worlds, commands and reference-side window statistics for the observation kernels' limits (k_observe modes 0-4,
-k_observe_redo, k_observe_list in sf_api.hip).  Test helper only.
+k_observe_redo, k_observe_list in sf_obs_kernels.hpp).  Test helper only.
 
 Every limit of those kernels is a count over one agent's 31 x 31 window.  The statistics here restate those counts from the
 ORACLE alone (its dump() and its own observation), never from the device, so that a test can say which path a window must
@@ -27,7 +27,7 @@ from strikeforce_amd import abi, config
 W = abi.OBS_WINDOW
 W2 = W * W
 MARK = 0xFFFFFFFF
-PLAIN = (0x01, 0x04, 0x08, 0x10, 0x20, 0x60, 0xA0, 0xE0)  # '#', '^', 'v', 'O', chest types 0-3: sf_api.hip obs_class_of
+PLAIN = (0x01, 0x04, 0x08, 0x10, 0x20, 0x60, 0xA0, 0xE0)  # '#', '^', 'v', 'O', chest types 0-3: sf_obs_kernels.hpp obs_class_of
 CENTRE = [(14, 15), (15, 14), (15, 15), (15, 16), (16, 15)]  # the network's pov cells, Modules.hpp:114-121
 
 

@@ -3,8 +3,8 @@ take the fallbacks that no game reaches at the product's limits: the dense kerne
 place), the list kernel's (the same, past the host-built table), its cell limit and last compaction pass at 65..128 cells,
 mode 3's unstaged branch, and spills / crowded markers in most steps.  Test helper only.
 
-The limits are compile-time constants of sf_api.hip with #ifndef defaults; nothing else differs from the product build,
-and the product build defines none of them.  Loaded through SF_LIBRARY_PATH in a child process (the path is read once per
+The limits are compile-time constants of sf_obs_kernels.hpp (which sf_api.hip includes) with #ifndef defaults; nothing
+else differs from the product build, and the product build defines none of them.  Loaded through SF_LIBRARY_PATH in a child process (the path is read once per
 process): tests/obs_edges_child.py."""
 import os
 import subprocess
@@ -13,8 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "strikeforce_amd", "csrc")
 LIB = os.path.join(ROOT, "tests", "libsf_obs_small.so")
 
-# the product's limits (the #ifndef defaults in sf_api.hip) and the small flavour's.  rec = own records of the dense
-# kernel (OBS_REC_MAX less its 8 shared class records), list = its pow queue, staged = mode 3's staging area;
+# the product's limits (the #ifndef defaults in sf_obs_kernels.hpp) and the small flavour's.  rec = own records of the
+# dense kernel (OBS_REC_MAX less its 8 shared class records), list = its pow queue, staged = mode 3's staging area;
 # ol_* = k_observe_list's own records, pow queue and non-empty cells.
 PRODUCT = {"rec": 64, "list": 256, "staged": 1922, "ol_rec": 48, "ol_powq": 384, "ol_cells": 640}
 SMALL = {"rec": 16, "list": 16, "staged": 256, "ol_rec": 30, "ol_powq": 16, "ol_cells": 128}

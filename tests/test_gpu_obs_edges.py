@@ -1,4 +1,4 @@
-"""The observation kernels (k_observe modes 0-4, k_observe_redo, k_observe_list; sf_api.hip) at every limit, fallback and
+"""The observation kernels (k_observe modes 0-4, k_observe_redo, k_observe_list; sf_obs_kernels.hpp) at every limit, fallback and
 write mode, against the oracle.  The CPU wave emulator only calls sf_obs.hpp's per-cell functions, so the kernels' own
 machinery — record tables, pow queues, compaction passes, non-zero bitmaps, delta bookkeeping, spill paths — is checked
 here and nowhere else.

@@ -22,10 +22,10 @@ def report(name, lim):
 
 
 def test_the_limits_are_the_kernels():
-    """obs_flavour.PRODUCT restates sf_api.hip's defaults, and the small flavour satisfies its static asserts."""
+    """obs_flavour.PRODUCT restates sf_obs_kernels.hpp's defaults, and the small flavour satisfies its static asserts."""
     import os
     import re
-    src = open(os.path.join(obs_flavour.CSRC, "sf_api.hip")).read()
+    src = open(os.path.join(obs_flavour.CSRC, "sf_obs_kernels.hpp")).read()
     got = {m.group(1): m.group(2) for m in re.finditer(r"#define (SF_O\w+) (.+)", src)}
     assert got == {"SF_OBS_REC_MAX": "72", "SF_OBS_LIST_MAX": "256", "SF_OBS_STAGED": "(2 * OBS_W2)", "SF_OL_REC": "48",
                    "SF_OL_POWQ": "384", "SF_OL_CELLS": "640"}
