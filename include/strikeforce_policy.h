@@ -141,6 +141,61 @@ typedef struct sf_policy_predict_io {
 } sf_policy_predict_io;
 int sf_policy_predict_sparse(sf_policy *p, const sf_policy_predict_io *io, int32_t agents);
 
+/* ---- bot-1's reward network (StrikeForce-client/bots/bot-1/RewardNet.hpp) -------------------------------------------
+ * The newer bots evaluate a second network every tick: RewardNet::get_reward(one_hot(action), imitate, state)
+ * (Agent.hpp:227, RewardNet.hpp:244-259) runs the GAIL discriminator RewardModel on the observation and the action just
+ * drawn and returns log D — the only per-step reward the reference has.  RewardModel (RewardNet.hpp:138-167) is the
+ * network above with one head: ResB, GameCNN and Backbone (RewardNet.hpp:26-136) are Modules.hpp:26-136 character for
+ * character, and its head is AgentModel's `value` head, ResB(160, 3) + Linear(160, 1) + sigmoid (:147-149, :161-165).
+ * What differs: forward(action, x) calls update_actions(action) first (:162), so the one-hot inside pov is the action of
+ * THIS tick; there is no policy head; the caller takes torch::log of the output (:257).
+ *
+ * A reward model is an sf_policy object of a second kind.  It has its own recurrent state per agent (every game builds a
+ * new Agent and with it a new RewardNet, Agent.hpp:95) and shares sf_policy_destroy, sf_policy_reset_memory(_n),
+ * sf_policy_get_memory / _set_memory, sf_policy_set_stream / _synchronize, sf_policy_kernel_time* and
+ * sf_policy_sparse_overflows with the policy.  The entries that evaluate a network are per kind: sf_policy_forward*,
+ * sf_policy_predict_sparse, sf_policy_act and sf_policy_features on a reward model, or sf_reward_forward /
+ * sf_reward_sparse on a policy, return SF_ERR_STATE.  Inference only: training (RewardNet.hpp:265-) is out of
+ * scope, as the PPO learner is.
+ *
+ * new RewardNet + load of RewardModel's parameters (RewardNet.hpp:172-216): the backbone.* and value.* fields of w; the
+ * policy_* fields are not looked at and may be NULL.  Same environment switches as sf_policy_create (SF_POLICY_LAYERED,
+ * SF_POLICY_FUSED_TAIL, ...).  Memory starts as after reset_memory(). */
+int sf_reward_create(const sf_policy_weights *w, int32_t max_agents, int32_t device, sf_policy **out);
+
+/* RewardModel::forward(one_hot(d_action[a]), obs) (RewardNet.hpp:161-166) for agents [0, agents) on the dense
+ * observation, the cross-check form as sf_policy_forward is for the policy: d_disc[a] = sigmoid(value head)  (:165),
+ * d_reward[a] = the f32 log of d_disc[a], the f32 value as stored, rounded once (:257; D == 0 gives -inf as torch::log
+ * does, never NaN).  Either output may be NULL, not both.  d_action (device, int32 per agent) is the index of the action drawn this
+ * tick — sf_policy_predict_sparse's d_action; an index outside [0, 9) means 0, "no action" (undefined in the reference).
+ * Its one-hot is the agent's action_input after the call (what update_actions leaves; sf_policy_get_memory shows it),
+ * and every agent's h_state advances. */
+int sf_reward_forward(sf_policy *r, const float *d_obs, const int32_t *d_action, int32_t agents, float *d_disc, float *d_reward);
+
+/* The same on the observation in list form, with the restart flags folded in: the hot path, two launches and no host
+ * synchronisation, to be issued right behind sf_policy_predict_sparse on the same stream (it reads that call's
+ * d_action).  Needs the fused tail.
+ *   d_keys .. cap, d_dense                            as in sf_policy_predict_io; same results as sf_reward_forward on the
+ *                                                     dense image bit for bit
+ *   d_reset_mask / d_reset_words, reset_stride, reset_group   as in sf_policy_predict_io: a restarted game's agent starts
+ *                                                     from h = 0 (a new RewardNet, Agent.hpp:95); its action slot is still
+ *                                                     the action given, since forward() overwrites what reset_memory() sets
+ *   d_action, d_disc, d_reward                        as in sf_reward_forward */
+typedef struct sf_reward_io {
+  const uint32_t *d_keys;
+  const float *d_vals;
+  const uint32_t *d_counts;
+  const float *d_pov;
+  int32_t cap;
+  const float *d_dense;
+  const uint8_t *d_reset_mask;
+  const int32_t *d_reset_words;
+  int32_t reset_stride, reset_group;
+  const int32_t *d_action;
+  float *d_disc, *d_reward;
+} sf_reward_io;
+int sf_reward_sparse(sf_policy *r, const sf_reward_io *io, int32_t agents);
+
 /* Read/write one agent's recurrent state for tests: h [2][160] and the action one-hot [9] (host buffers). */
 int sf_policy_get_memory(sf_policy *p, int32_t agent, float *h, float *action_input);
 int sf_policy_set_memory(sf_policy *p, int32_t agent, const float *h, const float *action_input);

@@ -8,6 +8,8 @@
 // The reference runs it with batch 1 on the host; here a "row" is one agent and all matrix work is f32 MFMA
 // (v_mfma_f32_32x32x2_f32: f32 in, f32 accumulate, bit-for-bit a k-ordered fmaf chain), so results differ from
 // libtorch only by summation order.
+// bot-1's RewardModel (bots/bot-1/RewardNet.hpp:138-167: the same backbone, the value head alone, the action of this tick in
+// pov, log of the output) is a second kind of the same object: sf_reward_*, k_tail<true>.
 //
 // Kernels
 //   k_gemm<WAVES, MODE>   C[M][N] = A[M][K] * W[N][K]^T (+ bias), LDS-tiled, 32 rows x 160 columns per wave
@@ -1109,6 +1111,9 @@ __device__ inline Row3 row_norm(const Row3 &x) {
   return y;
 }
 __device__ inline float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+// the f32 log of an f32, rounded once (the device's logf was two f32 steps from that on half of the reward tests' inputs; one
+// lane per agent takes it: the f64 path costs nothing that shows); log_f32(0) = -inf
+__device__ inline float log_f32(float x) { return (float)log((double)x); }
 
 // torch GRU cell, gate order r,z,n; gi = W_ih x + b_ih, gh = W_hh h + b_hh (both from k_gemm):
 //   r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r * gh_n), h' = (1 - z) * n + z * h
@@ -1143,9 +1148,17 @@ __global__ __launch_bounds__(256) void k_norm(const float *x, float *y, float *y
 
 // gru0 + the assembly of `combined` (Modules.hpp:110-123): comb[0:160] = norm(h0') + feat_n,
 // comb[160:329] = norm(pov), comb[329:352] = 0 (K padding)
+// action_in (a reward model, RewardNet.hpp:162 update_actions(action) in front of the backbone): the one-hot is that of the
+// action given — outside [0, 9): "no action" — and is stored as the agent's action_input; null: the stored row is read
 __global__ __launch_bounds__(256) void k_gru0(const float *gi, const float *gh, float *h, const float *feat_n,
-                                              const float *obs, const float *action_input, float *comb, int agents) {
+                                              const float *obs, float *action_input, const int32_t *action_in, float *comb, int agents) {
   SFP_ROW_PROLOGUE
+  int given = 0;
+  if (action_in) {
+    given = action_in[a];
+    given = (uint32_t)given < (uint32_t)ACT ? given : 0;
+    if (l < ACT) action_input[(size_t)a * ACT + l] = (l == given) ? 1.f : 0.f;
+  }
   float *hp = h + (size_t)a * HID;
   const Row3 hn = gru_cell(gi + (size_t)a * G3, gh + (size_t)a * G3, row_load(hp, l), l);
   row_store(hp, l, hn);
@@ -1169,7 +1182,7 @@ __global__ __launch_bounds__(256) void k_gru0(const float *gi, const float *gh, 
       const int dx = (cell == 1) ? -1 : (cell == 3) ? 1 : 0;
       v = op[(size_t)ch * OBS_W * OBS_W + (OBS_W / 2 + dy) * OBS_W + (OBS_W / 2 + dx)];
     } else if (e < POV) {
-      v = action_input[(size_t)a * ACT + (e - 5 * OBS_C)];
+      v = action_in ? ((e - 5 * OBS_C == given) ? 1.f : 0.f) : action_input[(size_t)a * ACT + (e - 5 * OBS_C)];
     }
     pv[i] = v;
     s += fabsf(v);
@@ -1236,6 +1249,19 @@ __global__ __launch_bounds__(256) void k_heads(const float *xp, const float *xv,
     probs[(size_t)a * ACT + l] = mine / s + 1e-8f;
   }
   if (l == 0) value[a] = sigmoidf_(val);
+}
+
+// the reward model's output layer (RewardNet.hpp:165, :257): D = sigmoid(W x + b), reward = log D — the log of the f32 D as
+// stored (D == 0: -inf, as torch::log gives).  Either output may be null.
+__global__ __launch_bounds__(256) void k_reward_head(const float *x, const float *wv, const float *bv, float *disc, float *reward,
+                                                     int agents) {
+  SFP_ROW_PROLOGUE
+  const Row3 v = row_load(x + (size_t)a * HID, l), wr = row_load(wv, l);
+  const float d = sigmoidf_(wave_sum(v.v[0] * wr.v[0] + v.v[1] * wr.v[1] + v.v[2] * wr.v[2]) + bv[0]);
+  if (l == 0) {
+    if (disc) disc[a] = d;
+    if (reward) reward[a] = log_f32(d);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1330,6 +1356,10 @@ struct TailArgs {
   uint64_t seed, draw;
   uint8_t *cmd;
   int32_t *action;
+  // k_tail<true>, a reward model (sf_reward_*): the action just drawn, whose one-hot is this call's action_input
+  // (RewardNet.hpp:162), and where log D goes (D itself goes to `value`); either output may be null
+  const int32_t *action_in;
+  float *reward;
 };
 
 // out[r][n0 + c] = bias[n0 + c] + sum_k in[r][k] * W[n0 + c][k] for the 16 agents r and 16 columns c of one tile
@@ -1473,7 +1503,13 @@ __device__ uint32_t sf_diag_tail[4096 * 16 * 24];  // [workgroup][wave][phase]
 #else
 #define TL_STAMP(ph)
 #endif
+// REWARD: the instance for bot-1's RewardModel (RewardNet.hpp:138-167) — the same backbone, then ONE head.  What differs:
+// the action one-hot in pov is that of t.action_in (update_actions runs in front of the backbone there) and is stored as
+// the agent's action_input; the ResB layers and the output layer are the tiles of one head (slot 0 of res_w / head_w holds
+// the value head: 10 tiles a layer, waves 10..15 have none and fetch nothing); the last lines store D = sigmoid and log D.
+template <bool REWARD>
 __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
+  constexpr int NH = REWARD ? 1 : 2;  // heads
   extern __shared__ __attribute__((aligned(16))) float tl[];
 #ifdef SF_DIAG_TAIL
   unsigned long long tl_last_ = __builtin_amdgcn_s_memtime();
@@ -1502,6 +1538,8 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
   const int32_t *fwp = t.reset_words ? t.reset_words + (size_t)(a / t.reset_group) * (size_t)t.reset_stride : reinterpret_cast<const int32_t *>(t.h[0]);
   const uint8_t fm = *fmp;
   const int32_t fw = *fwp;
+  int given = 0;
+  if (REWARD) given = t.action_in[a];
   Row3 h0 = row_load(t.h[0] + (size_t)a * HID, l), h1 = row_load(t.h[1] + (size_t)a * HID, l);
   float pvv[3];
   {
@@ -1515,7 +1553,7 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
         const int dy = (cell == 0) ? -1 : (cell == 4) ? 1 : 0;
         const int dx = (cell == 1) ? -1 : (cell == 3) ? 1 : 0;
         src = t.pov ? t.pov + (size_t)a * (5 * OBS_C) + e : op + (size_t)ch * OBS_W * OBS_W + (OBS_W / 2 + dy) * OBS_W + (OBS_W / 2 + dx);
-      } else if (e < POV) {
+      } else if (e < POV && !REWARD) {
         src += e - 5 * OBS_C;
       }
       pvv[i] = *src;
@@ -1526,6 +1564,10 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
   // a restarted game's agent is a new Agent (gameplay.hpp:481): zero memory, "no action" as its last action
   const bool fresh = __builtin_amdgcn_readfirstlane((int)((t.reset_mask && fm != 0) || (t.reset_words && fw != 0))) != 0;  // (uniform over the wave)
   if (fresh) h0 = Row3{}, h1 = Row3{};
+  if (REWARD) {  // an index outside [0, 9) means "no action"; update_actions leaves the one-hot in the agent's memory
+    given = (uint32_t)given < (uint32_t)ACT ? given : 0;
+    if (valid && l < ACT) t.action_input[(size_t)a * ACT + l] = (l == given) ? 1.f : 0.f;
+  }
   if (!t.feat) {  // conv3's input (act2 row = 9 pixels x 160 channels, the K order of the permuted weight)
     const f32x4 *src = reinterpret_cast<const f32x4 *>(t.act2 + (size_t)a * (9 * HID));
     f32x4 *dst = reinterpret_cast<f32x4 *>(tl + TL_A + w * TL_LDX);
@@ -1538,7 +1580,7 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
     const int e = l + 64 * i;
     float v = 0.f;
     if (e < 5 * OBS_C) v = pvv[i];
-    else if (e < POV) v = fresh ? (e == 5 * OBS_C ? 1.f : 0.f) : pvv[i];
+    else if (e < POV) v = REWARD ? (e - 5 * OBS_C == given ? 1.f : 0.f) : fresh ? (e == 5 * OBS_C ? 1.f : 0.f) : pvv[i];
     tl[TL_PV + w * TL_LDP + e] = v;
   }
   if (t.feat) {  // feat_n is a row of the wave's own agent                                                     :108
@@ -1614,6 +1656,7 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
     ts_tile160(tl + (hh ? TL_B1 : TL_B2), TL_LD, gru_wp(1, tt), hh ? t.gru_b_hh[1] : t.gru_b_ih[1], tl + (hh ? TL_GH : TL_GI), G3, n0, l,
                b0, b1, [&](TsBuf b) {
                  if (tt + TL_R < 2 * (G3 / 16)) return ts_issue<5>(b, gru_wp(1, tt + TL_R), 0);
+                 if (REWARD && w >= HID / 16) return b;   // (one head: this wave has no ResB tile)
                  return ts_issue<5>(b, res_wp(0, w), 0);  // next: the first ResB layer
                });
   }
@@ -1629,19 +1672,19 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
     for (int i = 0; i < 3; ++i) o.v[i] = on.v[i] + gn.v[i];
     const Row3 xn = row_norm(o);
     row_store(tl + TL_X0 + w * TL_LD, l, xn);
-    row_store(tl + TL_X1 + w * TL_LD, l, xn);
+    if (NH == 2) row_store(tl + TL_X1 + w * TL_LD, l, xn);
   }
   TL_STAMP(14);
   tail_barrier();
   TL_STAMP(15);
-  for (int i = 0; i < 3; ++i) {  // ResB layers of the two heads                                           :41-48
-    for (int tt = w; tt < 2 * (HID / 16); tt += TL_R) {
+  for (int i = 0; i < 3; ++i) {  // ResB layers of the two heads (REWARD: of the one)                      :41-48
+    for (int tt = w; tt < NH * (HID / 16); tt += TL_R) {
       const int hd = tt >= HID / 16, n0 = 16 * (tt - hd * (HID / 16));
       ts_tile160(tl + (hd ? TL_X1 : TL_X0), TL_LD, res_wp(i, tt), t.res_b[hd][i], tl + (hd ? TL_LIN1 : TL_LIN0), TL_LD, n0, l, b0, b1,
                  [&](TsBuf b) {
-                   if (tt + TL_R < 2 * (HID / 16)) return ts_issue<5>(b, res_wp(i, tt + TL_R), 0);
+                   if (tt + TL_R < NH * (HID / 16)) return ts_issue<5>(b, res_wp(i, tt + TL_R), 0);
                    if (i < 2) return ts_issue<5>(b, res_wp(i + 1, w), 0);
-                   if (w < 2) return ts_issue<5>(b, ts_wp(t.head_w[w], HID, 0, l), 0);  // next: the output layers
+                   if (w < NH) return ts_issue<5>(b, ts_wp(t.head_w[w], HID, 0, l), 0);  // next: the output layers
                    return b;
                  });
     }
@@ -1649,7 +1692,7 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
     tail_barrier();
     TL_STAMP(17);
 #pragma unroll
-    for (int hd = 0; hd < 2; ++hd) {
+    for (int hd = 0; hd < NH; ++hd) {
       float *xp = tl + (hd ? TL_X1 : TL_X0) + w * TL_LD;
       const Row3 y = row_load(tl + (hd ? TL_LIN1 : TL_LIN0) + w * TL_LD, l), xv = row_load(xp, l);
       Row3 r;
@@ -1663,13 +1706,19 @@ __global__ __launch_bounds__(TL_T) void k_tail(TailArgs t) {
   }
   // p = softmax(W_p x_p + b_p) + 1e-8, v = sigmoid(W_v x_v + b_v)                                           :172-175
   // (the two output layers as one MFMA tile each: weights padded with zero rows to 16 columns)
-  if (w < 2)
+  if (w < NH)
     ts_tile160(tl + (w ? TL_X1 : TL_X0), TL_LD, ts_wp(t.head_w[w], HID, 0, l), t.head_b[w], tl + (w ? TL_LIN1 : TL_LIN0), TL_LD, 0, l, b0, b1,
                [&](TsBuf b) { return b; });
   TL_STAMP(20);
   tail_barrier();
   TL_STAMP(21);
-  if (valid) {
+  if (REWARD) {  // D = sigmoid(value head), reward = log of the f32 D (D == 0: -inf)     RewardNet.hpp:165, :257
+    if (valid && l == 0) {
+      const float d = sigmoidf_(tl[TL_LIN0 + w * TL_LD]);
+      if (t.value) t.value[a] = d;
+      if (t.reward) t.reward[a] = log_f32(d);
+    }
+  } else if (valid) {
     const float *lg = tl + TL_LIN0 + w * TL_LD;
     float mx = lg[0];
 #pragma unroll
@@ -1772,6 +1821,9 @@ static std::vector<uint16_t> split_weights(const float *W, int N, int K) {
 
 struct Policy {
   int device = 0, max_agents = 0;
+  // sf_reward_create: bot-1's RewardModel (RewardNet.hpp:138-167) — the same backbone and ONE head, kept in slot 0 of
+  // res_w / res_b / head_w / head_b (slot 1 stays empty); evaluated by sf_reward_forward / sf_reward_sparse only
+  bool reward = false;
   hipStream_t stream = nullptr;
   uint64_t draws = 0;
   // parameters
@@ -1785,7 +1837,7 @@ struct Policy {
   bool folded = true;         // SF_POLICY_LAYERED=1: the four convolutions one after the other instead (cross-check, tests)
   float *conv_w[4] = {}, *gru_w_ih[2] = {}, *gru_w_hh[2] = {}, *gru_b_ih[2] = {}, *gru_b_hh[2] = {};
   float *comb_w = nullptr, *comb_b = nullptr;
-  float *res_w[2][3] = {}, *res_b[2][3] = {}, *head_w[2] = {}, *head_b[2] = {};  // [0] policy, [1] value
+  float *res_w[2][3] = {}, *res_b[2][3] = {}, *head_w[2] = {}, *head_b[2] = {};  // [0] policy, [1] value (reward model: [0] value)
   float *head_w16[2] = {}, *head_b16[2] = {};  // the same padded with zero rows to one 16-column MFMA tile (k_tail)
   // k_tail's copies of its matrices in the order its weight stream reads them (stage_tiles), ONE block in the order of use
   // (2.09 MB)
@@ -1936,7 +1988,7 @@ static int check_agents(Policy *p, int agents) {
   return SF_OK;
 }
 
-static int create(const sf_policy_weights *w, int max_agents, int device, sf_policy **out) {
+static int create(const sf_policy_weights *w, int max_agents, int device, sf_policy **out, bool reward = false) {
   if (!w || !out) return fail(SF_ERR_ARG, "null argument");
   if (w->abi_version != SF_POLICY_ABI_VERSION) return fail(SF_ERR_ARG, "sf_policy_weights.abi_version mismatch");
   if (max_agents < 1 || max_agents > (1 << 20)) return fail(SF_ERR_ARG, "max_agents must be 1..1048576");
@@ -1946,7 +1998,7 @@ static int create(const sf_policy_weights *w, int max_agents, int device, sf_pol
   if (device < 0 || device >= n) return fail(SF_ERR_DEVICE, "device ordinal out of range");
   SFP_HIP(hipSetDevice(device));
   Policy *p = new Policy();
-  p->device = device, p->max_agents = max_agents;
+  p->device = device, p->max_agents = max_agents, p->reward = reward;
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
@@ -2022,7 +2074,8 @@ static int create(const sf_policy_weights *w, int max_agents, int device, sf_pol
     p->f32_conv = e && e[0] == '1';
     const char *ft = getenv("SF_POLICY_FUSED_TAIL");
     p->fused_tail = !(ft && ft[0] == '0');
-    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_tail), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TL_LDS) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_tail<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TL_LDS) != hipSuccess ||
+        hipFuncSetAttribute(reinterpret_cast<const void *>(k_tail<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)TL_LDS) != hipSuccess)
       SFP_TRY(fail(SF_ERR_DEVICE, "k_tail needs 155 KB of LDS per workgroup"));
     if (hipFuncSetAttribute(reinterpret_cast<const void *>(k_gemm_b3<MODE_NHWC>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)B3_LDS) != hipSuccess ||
@@ -2049,23 +2102,24 @@ static int create(const sf_policy_weights *w, int max_agents, int device, sf_pol
     SFP_TRY(p->stage_tiles(&p->gru_w_hh_t[1], w->gru_w_hh[1], G3, HID));
     SFP_TRY(p->upload(&p->comb_b, w->comb_b, HID));
   }
-  for (int i = 0; i < 3; ++i) {
-    SFP_TRY(p->upload(&p->res_w[0][i], w->policy_res_w[i], (size_t)HID * HID));
-    SFP_TRY(p->stage_tiles(&p->res_w_t[0][i], w->policy_res_w[i], HID, HID));
-    SFP_TRY(p->stage_tiles(&p->res_w_t[1][i], w->value_res_w[i], HID, HID));
-    SFP_TRY(p->upload(&p->res_b[0][i], w->policy_res_b[i], HID));
-    SFP_TRY(p->upload(&p->res_w[1][i], w->value_res_w[i], (size_t)HID * HID));
-    SFP_TRY(p->upload(&p->res_b[1][i], w->value_res_b[i], HID));
-  }
-  SFP_TRY(p->upload(&p->head_w[0], w->policy_w, (size_t)ACT * HID));
-  SFP_TRY(p->upload(&p->head_b[0], w->policy_b, ACT));
-  SFP_TRY(p->upload(&p->head_w[1], w->value_w, HID));
-  SFP_TRY(p->upload(&p->head_b[1], w->value_b, 1));
-  for (int g = 0; g < 2; ++g) {
-    const int rows = g ? 1 : ACT;
+  // head slot -> the head it holds: a reward model has the value head alone (the policy_* fields are not looked at), and
+  // only its three ResB matrices and output layer enter k_tail's block
+  const int heads = reward ? 1 : 2;
+  for (int i = 0; i < 3; ++i)
+    for (int g = 0; g < heads; ++g) {
+      const bool val = reward || g;
+      SFP_TRY(p->upload(&p->res_w[g][i], val ? w->value_res_w[i] : w->policy_res_w[i], (size_t)HID * HID));
+      SFP_TRY(p->stage_tiles(&p->res_w_t[g][i], val ? w->value_res_w[i] : w->policy_res_w[i], HID, HID));
+      SFP_TRY(p->upload(&p->res_b[g][i], val ? w->value_res_b[i] : w->policy_res_b[i], HID));
+    }
+  for (int g = 0; g < heads; ++g) {
+    const bool val = reward || g;
+    const int rows = val ? 1 : ACT;
+    SFP_TRY(p->upload(&p->head_w[g], val ? w->value_w : w->policy_w, (size_t)rows * HID));
+    SFP_TRY(p->upload(&p->head_b[g], val ? w->value_b : w->policy_b, rows));
     std::vector<float> wpad((size_t)16 * HID, 0.f), bpad(16, 0.f);
-    std::memcpy(wpad.data(), g ? w->value_w : w->policy_w, (size_t)rows * HID * sizeof(float));
-    std::memcpy(bpad.data(), g ? w->value_b : w->policy_b, (size_t)rows * sizeof(float));
+    std::memcpy(wpad.data(), val ? w->value_w : w->policy_w, (size_t)rows * HID * sizeof(float));
+    std::memcpy(bpad.data(), val ? w->value_b : w->policy_b, (size_t)rows * sizeof(float));
     SFP_TRY(p->upload(&p->head_w16[g], wpad.data(), wpad.size()));
     SFP_TRY(p->stage_tiles(&p->head_w16_t[g], wpad.data(), 16, HID));
     SFP_TRY(p->upload(&p->head_b16[g], bpad.data(), bpad.size()));
@@ -2117,12 +2171,32 @@ struct PredictExtra {  // what sf_policy_predict_sparse folds into k_tail (see T
   uint8_t *cmd;
   int32_t *action;
 };
+struct RewardExtra {  // a reward model's forward (sf_reward_forward, sf_reward_sparse): see TailArgs
+  const int32_t *action;
+  float *disc, *reward;
+  const uint8_t *reset_mask;
+  const int32_t *reset_words;
+  int reset_stride, reset_group;
+};
+// every entry point that evaluates a network is for one kind of object
+static int check_kind(const Policy *p, bool reward, const char *entry) {
+  if (!p) return fail(SF_ERR_ARG, "null policy");
+  if (p->reward == reward) return SF_OK;
+  return fail(SF_ERR_STATE, std::string(entry) + (reward ? ": this object is a policy (sf_policy_create), not a reward model (sf_reward_create)"
+                                                         : ": this object is a reward model (sf_reward_create): sf_reward_forward and sf_reward_sparse evaluate it"));
+}
 static int forward(Policy *p, const float *d_obs, int agents, float *d_probs, float *d_value, const C0List *li = nullptr,
-                   const float *d_pov = nullptr, const PredictExtra *px = nullptr) {
+                   const float *d_pov = nullptr, const PredictExtra *px = nullptr, const RewardExtra *rx = nullptr) {
   int rc = check_agents(p, agents);
   if (rc) return rc;
-  if ((!d_obs && !li) || !d_probs || !d_value) return fail(SF_ERR_ARG, "null buffer");
-  if (li && !p->fused_tail) return fail(SF_ERR_STATE, "sf_policy_forward_sparse needs the fused tail (SF_POLICY_FUSED_TAIL=0 is set)");
+  if (p->reward != (rx != nullptr)) return fail(SF_ERR_STATE, "wrong kind of object for this forward");
+  if (rx) {
+    if ((!d_obs && !li) || !rx->action || (!rx->disc && !rx->reward)) return fail(SF_ERR_ARG, "null buffer");
+    if (li && !p->fused_tail) return fail(SF_ERR_STATE, "sf_reward_sparse needs the fused tail (SF_POLICY_FUSED_TAIL=0 is set)");
+  } else if ((!d_obs && !li) || !d_probs || !d_value) {
+    return fail(SF_ERR_ARG, "null buffer");
+  }
+  if (li && !rx && !p->fused_tail) return fail(SF_ERR_STATE, "sf_policy_forward_sparse needs the fused tail (SF_POLICY_FUSED_TAIL=0 is set)");
   if (px && !p->fused_tail) return fail(SF_ERR_STATE, "sf_policy_predict_sparse needs the fused tail (SF_POLICY_FUSED_TAIL=0 is set)");
   SFP_HIP(hipSetDevice(p->device));
   const dim3 rg((unsigned)((agents + 3) / 4)), rb(256);
@@ -2163,7 +2237,7 @@ static int forward(Policy *p, const float *d_obs, int agents, float *d_probs, fl
   if (p->fused_tail) {
     // (timed as one launch on the f32 pipe: conv3 unless folded + 4 GRU gate products + combined_processor + 6 ResB layers)
     hipEvent_t e1 = nullptr;
-    if ((rc = p->time_begin(2.0 * agents * ((p->folded ? 0.0 : (double)HID * 9 * HID) + 4.0 * G3 * HID + (double)HID * COMB_PAD + 6.0 * HID * HID), false, &e1, 3)))
+    if ((rc = p->time_begin(2.0 * agents * ((p->folded ? 0.0 : (double)HID * 9 * HID) + 4.0 * G3 * HID + (double)HID * COMB_PAD + (rx ? 3.0 : 6.0) * HID * HID), false, &e1, 3)))
       return rc;
     TailArgs t{};
     t.act2 = p->act[2], t.obs = d_obs, t.pov = d_pov, t.conv3_w = p->conv_w[3];
@@ -2171,7 +2245,9 @@ static int forward(Policy *p, const float *d_obs, int agents, float *d_probs, fl
     for (int g = 0; g < 2; ++g) {
       // (the matrices in k_tail's stream order, stage_tiles)
       t.gru_w_ih[g] = p->tail_w + p->gru_w_ih_t[g], t.gru_w_hh[g] = p->tail_w + p->gru_w_hh_t[g], t.gru_b_ih[g] = p->gru_b_ih[g], t.gru_b_hh[g] = p->gru_b_hh[g];
-      t.h[g] = p->h[g], t.head_w[g] = p->tail_w + p->head_w16_t[g], t.head_b[g] = p->head_b16[g];
+      t.h[g] = p->h[g];
+      if (g && rx) continue;  // (a reward model: one head, slot 0)
+      t.head_w[g] = p->tail_w + p->head_w16_t[g], t.head_b[g] = p->head_b16[g];
       for (int i = 0; i < 3; ++i) t.res_w[g][i] = p->tail_w + p->res_w_t[g][i], t.res_b[g][i] = p->res_b[g][i];
     }
     t.comb_w = p->tail_w + p->comb_w_t, t.comb_b = p->comb_b, t.action_input = p->action_input;
@@ -2183,9 +2259,16 @@ static int forward(Policy *p, const float *d_obs, int agents, float *d_probs, fl
       t.reset_group = px->reset_group > 0 ? px->reset_group : 1;
       t.act = 1, t.greedy = px->greedy, t.as = px->as, t.seed = px->seed, t.draw = p->draws++, t.cmd = px->cmd, t.action = px->action;
     }
-    hipLaunchKernelGGL(k_tail, dim3((unsigned)((agents + TL_R - 1) / TL_R)), dim3(TL_T), TL_LDS, st, t);
+    if (rx) {
+      t.action_in = rx->action, t.value = rx->disc, t.reward = rx->reward, t.probs = nullptr;
+      t.reset_mask = rx->reset_mask, t.reset_words = rx->reset_words, t.reset_stride = rx->reset_stride;
+      t.reset_group = rx->reset_group > 0 ? rx->reset_group : 1;
+    }
+    const dim3 tl_grid((unsigned)((agents + TL_R - 1) / TL_R));
+    if (rx) hipLaunchKernelGGL(k_tail<true>, tl_grid, dim3(TL_T), TL_LDS, st, t);
+    else hipLaunchKernelGGL(k_tail<false>, tl_grid, dim3(TL_T), TL_LDS, st, t);
 #ifdef SF_DIAG_TAIL  // (diagnostic build: the stamps of a second launch, whose weights the first one left in the L2s)
-    if (std::getenv("SF_DIAG_TAIL_TWICE")) hipLaunchKernelGGL(k_tail, dim3((unsigned)((agents + TL_R - 1) / TL_R)), dim3(TL_T), TL_LDS, st, t);
+    if (std::getenv("SF_DIAG_TAIL_TWICE") && !rx) hipLaunchKernelGGL(k_tail<false>, tl_grid, dim3(TL_T), TL_LDS, st, t);
 #endif
     SFP_HIP(hipGetLastError());
     if (e1) SFP_HIP(hipEventRecord(e1, st));
@@ -2198,7 +2281,8 @@ static int forward(Policy *p, const float *d_obs, int agents, float *d_probs, fl
   if ((rc = p->dense2(p->feat_n, p->gru_w_ih[0], p->gru_b_ih[0], p->gi, p->h[0], p->gru_w_hh[0], p->gru_b_hh[0], p->gh,
                       HID, G3, agents, G3, HID)))
     return rc;
-  hipLaunchKernelGGL(k_gru0, rg, rb, 0, st, p->gi, p->gh, p->h[0], p->feat_n, d_obs, p->action_input, p->comb, agents);
+  hipLaunchKernelGGL(k_gru0, rg, rb, 0, st, p->gi, p->gh, p->h[0], p->feat_n, d_obs, p->action_input, rx ? rx->action : (const int32_t *)nullptr,
+                     p->comb, agents);
   // combined_processor                                                                         :125-126
   if ((rc = p->dense(p->comb, COMB_PAD, p->comb_w, p->comb_b, p->gated, HID, agents, HID, COMB_PAD))) return rc;
   hipLaunchKernelGGL(k_norm, rg, rb, 0, st, p->gated, p->gated_n, none, agents);
@@ -2207,6 +2291,16 @@ static int forward(Policy *p, const float *d_obs, int agents, float *d_probs, fl
                       HID, G3, agents, G3, HID)))
     return rc;
   hipLaunchKernelGGL(k_gru1, rg, rb, 0, st, p->gi, p->gh, p->h[1], p->gated_n, p->out, agents);
+  if (rx) {  // a reward model's one head: ResB, Linear, sigmoid, log                          RewardNet.hpp:161-165, :257
+    hipLaunchKernelGGL(k_norm, rg, rb, 0, st, p->out, p->x[0], none, agents);
+    for (int i = 0; i < 3; ++i) {
+      if ((rc = p->dense(p->x[0], HID, p->res_w[0][i], p->res_b[0][i], p->lin[0], HID, agents, HID, HID))) return rc;
+      hipLaunchKernelGGL(k_res, dim3(rg.x, 1), rb, 0, st, p->lin[0], p->x[0], (const float *)nullptr, none, agents);
+    }
+    hipLaunchKernelGGL(k_reward_head, rg, rb, 0, st, p->x[0], p->head_w[0], p->head_b[0], rx->disc, rx->reward, agents);
+    SFP_HIP(hipGetLastError());
+    return SF_OK;
+  }
   // heads: ResB then Linear; layer i of both heads shares a launch                             :41-48,172-175
   hipLaunchKernelGGL(k_norm, rg, rb, 0, st, p->out, p->x[0], p->x[1], agents);
   for (int i = 0; i < 3; ++i) {
@@ -2254,13 +2348,39 @@ int sf_policy_reset_memory(sf_policy *pp, const uint8_t *d_mask) {
 }
 
 int sf_policy_forward(sf_policy *pp, const float *d_obs, int32_t agents, float *d_probs, float *d_value) {
+  if (int rc = sfp::check_kind(reinterpret_cast<Policy *>(pp), false, "sf_policy_forward")) return rc;
   return sfp::forward(reinterpret_cast<Policy *>(pp), d_obs, agents, d_probs, d_value);
+}
+
+int sf_reward_create(const sf_policy_weights *w, int32_t max_agents, int32_t device, sf_policy **out) {
+  return sfp::create(w, max_agents, device, out, true);
+}
+
+int sf_reward_forward(sf_policy *pp, const float *d_obs, const int32_t *d_action, int32_t agents, float *d_disc, float *d_reward) {
+  Policy *p = reinterpret_cast<Policy *>(pp);
+  if (int rc = sfp::check_kind(p, true, "sf_reward_forward")) return rc;
+  const sfp::RewardExtra rx{d_action, d_disc, d_reward, nullptr, nullptr, 0, 1};
+  return sfp::forward(p, d_obs, agents, nullptr, nullptr, nullptr, nullptr, nullptr, &rx);
+}
+
+int sf_reward_sparse(sf_policy *pp, const sf_reward_io *io, int32_t agents) {
+  Policy *p = reinterpret_cast<Policy *>(pp);
+  if (!p || !io) return sfp::fail(SF_ERR_ARG, "null policy or io");
+  if (int rc = sfp::check_kind(p, true, "sf_reward_sparse")) return rc;
+  if (!io->d_keys || !io->d_vals || !io->d_counts || !io->d_pov || io->cap < 1) return sfp::fail(SF_ERR_ARG, "null buffer or cap < 1");
+  if (io->cap > SF_POLICY_LIST_MAX) return sfp::fail(SF_ERR_ARG, "cap above SF_POLICY_LIST_MAX (2048)");
+  if (io->d_reset_words && (io->reset_stride < 1 || io->reset_group < 1)) return sfp::fail(SF_ERR_ARG, "reset_stride and reset_group must be positive");
+  const sfp::RewardExtra rx{io->d_action, io->d_disc, io->d_reward, io->d_reset_mask, io->d_reset_words, io->reset_stride, io->reset_group};
+  // (without d_dense: lists that do not fit are counted, as in sf_policy_forward_sparse)
+  const sfp::C0List li{io->d_keys, io->d_vals, io->d_counts, io->cap, io->d_dense ? nullptr : p->d_overflows};
+  return sfp::forward(p, io->d_dense, agents, nullptr, nullptr, &li, io->d_pov, nullptr, &rx);
 }
 
 int sf_policy_features(sf_policy *pp, const float *d_obs, int32_t agents, float *d_feat) {
   Policy *p = reinterpret_cast<Policy *>(pp);
-  int rc = sfp::check_agents(p, agents);
+  int rc = sfp::check_kind(p, false, "sf_policy_features");
   if (rc) return rc;
+  if ((rc = sfp::check_agents(p, agents))) return rc;
   if (!d_obs || !d_feat) return sfp::fail(SF_ERR_ARG, "null buffer");
   SFP_HIP(hipSetDevice(p->device));
   if (p->folded) {
@@ -2281,7 +2401,7 @@ int sf_policy_features(sf_policy *pp, const float *d_obs, int32_t agents, float 
 int sf_policy_forward_sparse(sf_policy *pp, const uint32_t *d_keys, const float *d_vals, const uint32_t *d_counts,
                              const float *d_pov, int32_t cap, int32_t agents, float *d_probs, float *d_value) {
   Policy *p = reinterpret_cast<Policy *>(pp);
-  if (!p) return sfp::fail(SF_ERR_ARG, "null policy");
+  if (int rc = sfp::check_kind(p, false, "sf_policy_forward_sparse")) return rc;
   if (!d_keys || !d_vals || !d_counts || !d_pov || cap < 1) return sfp::fail(SF_ERR_ARG, "null buffer or cap < 1");
   if (cap > SF_POLICY_LIST_MAX) return sfp::fail(SF_ERR_ARG, "cap above SF_POLICY_LIST_MAX (2048)");
   const sfp::C0List li{d_keys, d_vals, d_counts, cap, p->d_overflows};
@@ -2292,7 +2412,7 @@ int sf_policy_forward_sparse_or_dense(sf_policy *pp, const uint32_t *d_keys, con
                                       const float *d_pov, int32_t cap, int32_t agents, const float *d_dense, float *d_probs,
                                       float *d_value) {
   Policy *p = reinterpret_cast<Policy *>(pp);
-  if (!p) return sfp::fail(SF_ERR_ARG, "null policy");
+  if (int rc = sfp::check_kind(p, false, "sf_policy_forward_sparse_or_dense")) return rc;
   if (!d_keys || !d_vals || !d_counts || !d_pov || !d_dense || cap < 1) return sfp::fail(SF_ERR_ARG, "null buffer or cap < 1");
   // (above it the kernels' own list limit would call an agent "overflowed" whose dense row sf_observe_overflow_device,
   // which only knows cap, never wrote)
@@ -2304,6 +2424,7 @@ int sf_policy_forward_sparse_or_dense(sf_policy *pp, const uint32_t *d_keys, con
 int sf_policy_predict_sparse(sf_policy *pp, const sf_policy_predict_io *io, int32_t agents) {
   Policy *p = reinterpret_cast<Policy *>(pp);
   if (!p || !io) return sfp::fail(SF_ERR_ARG, "null policy or io");
+  if (int rc = sfp::check_kind(p, false, "sf_policy_predict_sparse")) return rc;
   if (!io->d_keys || !io->d_vals || !io->d_counts || !io->d_pov || io->cap < 1) return sfp::fail(SF_ERR_ARG, "null buffer or cap < 1");
   if (io->cap > SF_POLICY_LIST_MAX) return sfp::fail(SF_ERR_ARG, "cap above SF_POLICY_LIST_MAX (2048)");
   if (!io->d_cmd || !io->action_string) return sfp::fail(SF_ERR_ARG, "null buffer");
@@ -2339,8 +2460,9 @@ int sf_policy_sparse_overflows(sf_policy *pp, int32_t *count) {
 int sf_policy_act(sf_policy *pp, const float *d_probs, int32_t agents, const char *action_string, uint64_t seed,
                   int32_t greedy, uint8_t *d_cmd, int32_t *d_action) {
   Policy *p = reinterpret_cast<Policy *>(pp);
-  int rc = sfp::check_agents(p, agents);
+  int rc = sfp::check_kind(p, false, "sf_policy_act");
   if (rc) return rc;
+  if ((rc = sfp::check_agents(p, agents))) return rc;
   if (!d_probs || !d_cmd || !action_string) return sfp::fail(SF_ERR_ARG, "null buffer");
   if (std::strlen(action_string) != (size_t)sfp::ACT) return sfp::fail(SF_ERR_ARG, "action_string must have 9 chars");
   sfp::ActStr as;

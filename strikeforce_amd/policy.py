@@ -4,6 +4,8 @@
 arena batch on the GPU, straight from the observation buffer ``ArenaBatch.observe_device`` wrote.  Parameters are
 passed as a dict of float32 numpy arrays keyed by the reference's parameter names (``named_parameters()`` of
 ``AgentModel``); ``init_parameters`` makes a random set with torch's default initialisers for the same shapes.
+``RewardBatch`` does the same for the second network bot-1 runs every tick, the GAIL discriminator RewardModel
+(bots/bot-1/RewardNet.hpp:138-167): D and log D, the per-step reward, from the observation and the action just drawn.
 There is no CPU path: without the HIP library / a GPU this raises.
 """
 import ctypes as C
@@ -52,6 +54,12 @@ def parameter_shapes():
     return s
 
 
+def reward_parameter_shapes():
+    """name -> shape of bot-1's RewardModel (bots/bot-1/RewardNet.hpp:138-151): AgentModel's backbone.* and value.*
+    under the same names (value.0.lin{i}.*, value.1.*); it has no policy head."""
+    return {k: v for k, v in parameter_shapes().items() if not k.startswith("policy.")}
+
+
 def init_parameters(seed=0, gain=1.0):
     """Random parameters of the reference's shapes: U(-1/sqrt(fan_in), 1/sqrt(fan_in)) like torch's defaults for
     Conv2d / Linear, U(-1/sqrt(hidden), 1/sqrt(hidden)) for GRU.  (There is no network to fetch checkpoints.)"""
@@ -74,7 +82,8 @@ def load_checkpoint(path):
     (bots/bot-0.5/Agent.hpp:77-110,124,159-161) writes a TorchScript module archive whose named_parameters() carry the
     names AgentModel registered (Modules.hpp:37,62,87-91,147-152) — the names `parameter_shapes()` lists.  Also reads a
     plain state_dict saved from Python.  Returns {name: float32 numpy array}, every name and shape checked; nothing
-    is filled in silently."""
+    is filled in silently.  A RewardModel archive (bots/bot-1/RewardNet.hpp:239: no policy.* parameter in it) is held to
+    `reward_parameter_shapes()` instead and goes to `RewardBatch`."""
     import torch
     named = None
     try:
@@ -88,7 +97,8 @@ def load_checkpoint(path):
             raise ValueError("%s holds neither a TorchScript module nor a state_dict" % path)
         named = obj
     out = {}
-    for name, shape in parameter_shapes().items():
+    shapes = parameter_shapes() if any(k.startswith("policy.") for k in named) else reward_parameter_shapes()
+    for name, shape in shapes.items():
         if name not in named:
             raise ValueError("checkpoint %s lacks parameter %s" % (path, name))
         a = named[name].detach().to(torch.float32).contiguous().numpy()
@@ -109,10 +119,21 @@ class PredictIO(C.Structure):
                 ("greedy", C.c_int32), ("d_probs", C.c_void_p), ("d_value", C.c_void_p), ("d_cmd", C.c_void_p), ("d_action", C.c_void_p)]
 
 
+class RewardIO(C.Structure):
+    """sf_reward_io (include/strikeforce_policy.h)."""
+    _fields_ = [("d_keys", C.c_void_p), ("d_vals", C.c_void_p), ("d_counts", C.c_void_p), ("d_pov", C.c_void_p), ("cap", C.c_int32),
+                ("d_dense", C.c_void_p), ("d_reset_mask", C.c_void_p), ("d_reset_words", C.c_void_p),
+                ("reset_stride", C.c_int32), ("reset_group", C.c_int32), ("d_action", C.c_void_p), ("d_disc", C.c_void_p),
+                ("d_reward", C.c_void_p)]
+
+
 def _bind(L):
     if getattr(L, "_sf_policy_bound", False):
         return
     vp = C.c_void_p
+    L.sf_reward_create.argtypes = [C.POINTER(Weights), C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.sf_reward_forward.argtypes = [vp, vp, vp, C.c_int32, vp, vp]
+    L.sf_reward_sparse.argtypes = [vp, C.POINTER(RewardIO), C.c_int32]
     L.sf_policy_predict_sparse.argtypes = [vp, C.POINTER(PredictIO), C.c_int32]
     L.sf_policy_create.argtypes = [C.POINTER(Weights), C.c_int32, C.c_int32, C.POINTER(vp)]
     L.sf_policy_destroy.argtypes = [vp]
@@ -135,7 +156,7 @@ def _bind(L):
     L.sf_policy_features.argtypes = [vp, vp, C.c_int32, vp]
     L.sf_policy_kernel_time.argtypes = [vp, C.c_int32, _FP, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.sf_policy_kernel_time_ex.argtypes = L.sf_policy_kernel_time.argtypes
-    for n in EXPORTS:
+    for n in EXPORTS + REWARD_EXPORTS:
         if n != "sf_policy_destroy":
             getattr(L, n).restype = C.c_int
     L._sf_policy_bound = True
@@ -149,14 +170,17 @@ EXPORTS = ["sf_policy_create", "sf_policy_destroy", "sf_policy_reset_memory", "s
            "sf_policy_kernel_time", "sf_policy_kernel_time_ex", "sf_policy_kernel_time_by_kernel", "sf_policy_gemm", "sf_policy_gemm_split", "sf_policy_features", "sf_policy_abi_version"]
 
 
-class PolicyBatch:
-    """`max_agents` independent copies of the reference's AgentModel state over one shared parameter set."""
+# the reward network's entries (sf_reward_*: the same header)
+REWARD_EXPORTS = ["sf_reward_create", "sf_reward_forward", "sf_reward_sparse"]
 
-    def __init__(self, params, max_agents, device=0):
+
+class _NetBatch:
+    """What a policy and a reward model share: one sf_policy handle, per-agent memory, stream, timers."""
+
+    def __init__(self, params, max_agents, device, shapes, create):
         self.L = env.load_library()
         _bind(self.L)
         self.max_agents = int(max_agents)
-        shapes = parameter_shapes()
         keep = {}
         for name, shape in shapes.items():
             if name not in params:
@@ -178,14 +202,16 @@ class PolicyBatch:
         w.comb_w, w.comb_b = ptr("backbone.combined_processor.0.weight"), ptr("backbone.combined_processor.0.bias")
         for i in range(RES_LAYERS):
             w.value_res_w[i], w.value_res_b[i] = ptr("value.0.lin%d.weight" % i), ptr("value.0.lin%d.bias" % i)
-            w.policy_res_w[i], w.policy_res_b[i] = ptr("policy.0.lin%d.weight" % i), ptr("policy.0.lin%d.bias" % i)
         w.value_w, w.value_b = ptr("value.1.weight"), ptr("value.1.bias")
-        w.policy_w, w.policy_b = ptr("policy.1.weight"), ptr("policy.1.bias")
+        if "policy.1.weight" in shapes:  # (a reward model has no policy head: those fields stay NULL)
+            for i in range(RES_LAYERS):
+                w.policy_res_w[i], w.policy_res_b[i] = ptr("policy.0.lin%d.weight" % i), ptr("policy.0.lin%d.bias" % i)
+            w.policy_w, w.policy_b = ptr("policy.1.weight"), ptr("policy.1.bias")
         self.h = C.c_void_p()
-        rc = self.L.sf_policy_create(C.byref(w), self.max_agents, int(device), C.byref(self.h))
+        rc = getattr(self.L, create)(C.byref(w), self.max_agents, int(device), C.byref(self.h))
         if rc != 0:
             self.h = None
-            raise env.StrikeForceError("sf_policy_create failed (%d): %s" % (rc, self.L.sf_last_error().decode()))
+            raise env.StrikeForceError("%s failed (%d): %s" % (create, rc, self.L.sf_last_error().decode()))
 
     def _ck(self, rc, what):
         if rc != 0:
@@ -217,6 +243,51 @@ class PolicyBatch:
         else:
             self._ck(self.L.sf_policy_reset_memory_n(self.h, m, int(agents)), "sf_policy_reset_memory_n")
 
+    def sparse_overflows(self):
+        """Agents evaluated on an empty observation since the last call because their list did not fit (synchronises)."""
+        n = C.c_int32()
+        self._ck(self.L.sf_policy_sparse_overflows(self.h, C.byref(n)), "sf_policy_sparse_overflows")
+        return n.value
+
+    def get_memory(self, agent):
+        h = np.zeros((2, HIDDEN), dtype=np.float32)
+        a = np.zeros(ACTIONS, dtype=np.float32)
+        self._ck(self.L.sf_policy_get_memory(self.h, int(agent), h.ctypes.data_as(_FP), a.ctypes.data_as(_FP)),
+                 "sf_policy_get_memory")
+        return h, a
+
+    def set_memory(self, agent, h, action_input):
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(2, HIDDEN)
+        a = np.ascontiguousarray(action_input, dtype=np.float32).reshape(ACTIONS)
+        self._ck(self.L.sf_policy_set_memory(self.h, int(agent), h.ctypes.data_as(_FP), a.ctypes.data_as(_FP)),
+                 "sf_policy_set_memory")
+
+    def kernel_time_by_pipe(self, enable=True):
+        """[(ms, flop, launches) of the f32-MFMA launches, (...) of the bf16-split launches] since the last call."""
+        ms, fl, n = (C.c_float * 2)(), (C.c_double * 2)(), (C.c_int32 * 2)()
+        self._ck(self.L.sf_policy_kernel_time_ex(self.h, 1 if enable else 0, ms, fl, n), "sf_policy_kernel_time_ex")
+        return [(ms[k], fl[k], n[k]) for k in range(2)]
+
+    def kernel_time_by_kernel(self, enable=True):
+        """[(ms, algorithmic flop, launches)] for k_gemm (f32 MFMA), k_gemm_b3 (bf16 split), conv0 on the non-zeros, k_tail."""
+        ms, fl, n = (C.c_float * 4)(), (C.c_double * 4)(), (C.c_int32 * 4)()
+        self._ck(self.L.sf_policy_kernel_time_by_kernel(self.h, 1 if enable else 0, ms, fl, n), "sf_policy_kernel_time_by_kernel")
+        return [(float(ms[k]), float(fl[k]), int(n[k])) for k in range(4)]
+
+    def kernel_time(self, enable=True):
+        """(ms, flop, launches) of the MFMA GEMM launches since the last call; arms / disarms the timers."""
+        ms, fl, n = C.c_float(), C.c_double(), C.c_int32()
+        self._ck(self.L.sf_policy_kernel_time(self.h, 1 if enable else 0, C.byref(ms), C.byref(fl), C.byref(n)),
+                 "sf_policy_kernel_time")
+        return ms.value, fl.value, n.value
+
+
+class PolicyBatch(_NetBatch):
+    """`max_agents` independent copies of the reference's AgentModel state over one shared parameter set."""
+
+    def __init__(self, params, max_agents, device=0):
+        super().__init__(params, max_agents, device, parameter_shapes(), "sf_policy_create")
+
     def forward(self, d_obs_ptr, agents, d_probs_ptr, d_value_ptr):
         self._ck(self.L.sf_policy_forward(self.h, C.c_void_p(d_obs_ptr), int(agents), C.c_void_p(d_probs_ptr),
                                           C.c_void_p(d_value_ptr)), "sf_policy_forward")
@@ -236,12 +307,6 @@ class PolicyBatch:
         self._ck(self.L.sf_policy_forward_sparse(self.h, C.c_void_p(d_keys_ptr), C.c_void_p(d_vals_ptr), C.c_void_p(d_counts_ptr),
                                                  C.c_void_p(d_pov_ptr), int(cap), int(agents), C.c_void_p(d_probs_ptr),
                                                  C.c_void_p(d_value_ptr)), "sf_policy_forward_sparse")
-
-    def sparse_overflows(self):
-        """Agents evaluated on an empty observation since the last call because their list did not fit (synchronises)."""
-        n = C.c_int32()
-        self._ck(self.L.sf_policy_sparse_overflows(self.h, C.byref(n)), "sf_policy_sparse_overflows")
-        return n.value
 
     def predict_sparse(self, d_keys_ptr, d_vals_ptr, d_counts_ptr, d_pov_ptr, cap, agents, d_probs_ptr, d_value_ptr, d_cmd_ptr,
                        seed=0, greedy=False, d_action_ptr=None, action_string=ACTION_STRING, d_dense_ptr=None, d_reset_mask_ptr=None,
@@ -263,19 +328,6 @@ class PolicyBatch:
                                       C.c_uint64(seed), 1 if greedy else 0, C.c_void_p(d_cmd_ptr),
                                       C.c_void_p(d_action_ptr) if d_action_ptr else None), "sf_policy_act")
 
-    def get_memory(self, agent):
-        h = np.zeros((2, HIDDEN), dtype=np.float32)
-        a = np.zeros(ACTIONS, dtype=np.float32)
-        self._ck(self.L.sf_policy_get_memory(self.h, int(agent), h.ctypes.data_as(_FP), a.ctypes.data_as(_FP)),
-                 "sf_policy_get_memory")
-        return h, a
-
-    def set_memory(self, agent, h, action_input):
-        h = np.ascontiguousarray(h, dtype=np.float32).reshape(2, HIDDEN)
-        a = np.ascontiguousarray(action_input, dtype=np.float32).reshape(ACTIONS)
-        self._ck(self.L.sf_policy_set_memory(self.h, int(agent), h.ctypes.data_as(_FP), a.ctypes.data_as(_FP)),
-                 "sf_policy_set_memory")
-
     def gemm(self, d_a_ptr, lda, d_w_ptr, d_bias_ptr, d_c_ptr, ldc, m, n, k):
         """The MFMA matrix kernel on its own: C = A W^T + bias on device buffers."""
         self._ck(self.L.sf_policy_gemm(self.h, C.c_void_p(d_a_ptr), lda, C.c_void_p(d_w_ptr),
@@ -292,21 +344,29 @@ class PolicyBatch:
                                              C.c_void_p(d_bias_ptr) if d_bias_ptr else None, C.c_void_p(d_c_ptr), ldc, m, n, k),
                  "sf_policy_gemm_split")
 
-    def kernel_time_by_pipe(self, enable=True):
-        """[(ms, flop, launches) of the f32-MFMA launches, (...) of the bf16-split launches] since the last call."""
-        ms, fl, n = (C.c_float * 2)(), (C.c_double * 2)(), (C.c_int32 * 2)()
-        self._ck(self.L.sf_policy_kernel_time_ex(self.h, 1 if enable else 0, ms, fl, n), "sf_policy_kernel_time_ex")
-        return [(ms[k], fl[k], n[k]) for k in range(2)]
 
-    def kernel_time_by_kernel(self, enable=True):
-        """[(ms, algorithmic flop, launches)] for k_gemm (f32 MFMA), k_gemm_b3 (bf16 split), conv0 on the non-zeros, k_tail."""
-        ms, fl, n = (C.c_float * 4)(), (C.c_double * 4)(), (C.c_int32 * 4)()
-        self._ck(self.L.sf_policy_kernel_time_by_kernel(self.h, 1 if enable else 0, ms, fl, n), "sf_policy_kernel_time_by_kernel")
-        return [(float(ms[k]), float(fl[k]), int(n[k])) for k in range(4)]
+class RewardBatch(_NetBatch):
+    """`max_agents` independent copies of bot-1's RewardModel state (bots/bot-1/RewardNet.hpp:138-167, one per Agent:
+    Agent.hpp:95) over one shared parameter set (`reward_parameter_shapes()`; policy.* entries of `params` are ignored).
+    D = the discriminator's output, reward = log D: what RewardNet::get_reward returns (RewardNet.hpp:244-259)."""
 
-    def kernel_time(self, enable=True):
-        """(ms, flop, launches) of the MFMA GEMM launches since the last call; arms / disarms the timers."""
-        ms, fl, n = C.c_float(), C.c_double(), C.c_int32()
-        self._ck(self.L.sf_policy_kernel_time(self.h, 1 if enable else 0, C.byref(ms), C.byref(fl), C.byref(n)),
-                 "sf_policy_kernel_time")
-        return ms.value, fl.value, n.value
+    def __init__(self, params, max_agents, device=0):
+        super().__init__(params, max_agents, device, reward_parameter_shapes(), "sf_reward_create")
+
+    def forward(self, d_obs_ptr, d_action_ptr, agents, d_disc_ptr=None, d_reward_ptr=None):
+        """RewardModel::forward(one_hot(action), obs) on the dense observation: D and / or log D per agent; the one-hot
+        stays in the agent's memory (update_actions)."""
+        self._ck(self.L.sf_reward_forward(self.h, C.c_void_p(d_obs_ptr), C.c_void_p(d_action_ptr), int(agents), C.c_void_p(d_disc_ptr),
+                                          C.c_void_p(d_reward_ptr)), "sf_reward_forward")
+
+    def reward_sparse(self, d_keys_ptr, d_vals_ptr, d_counts_ptr, d_pov_ptr, cap, agents, d_action_ptr, d_disc_ptr=None, d_reward_ptr=None,
+                      d_dense_ptr=None, d_reset_mask_ptr=None, reset_words=None):
+        """The same on ArenaBatch.observe_sparse_device's lists with the restart flags folded in (PolicyBatch.predict_sparse's
+        arguments): issue it right behind predict_sparse on the same stream with that call's d_action."""
+        io = RewardIO()
+        io.d_keys, io.d_vals, io.d_counts, io.d_pov, io.cap = d_keys_ptr, d_vals_ptr, d_counts_ptr, d_pov_ptr, int(cap)
+        io.d_dense, io.d_reset_mask = d_dense_ptr, d_reset_mask_ptr
+        if reset_words is not None:
+            io.d_reset_words, io.reset_stride, io.reset_group = reset_words
+        io.d_action, io.d_disc, io.d_reward = d_action_ptr, d_disc_ptr, d_reward_ptr
+        self._ck(self.L.sf_reward_sparse(self.h, C.byref(io), int(agents)), "sf_reward_sparse")
