@@ -376,6 +376,12 @@ int sf_synchronize(sf_env *env);
  * library's stream: *ms = sum of kernel durations, *launches = number of launches. */
 int sf_kernel_time(sf_env *env, int32_t enable, float *ms, int32_t *launches);
 
+/* Which step kernel the last sf_step / sf_step_device launch ran: *fixed_shape = the index of the built fixed shape
+ * (a kernel compiled for one listed configuration; the library picks it at sf_create where every fixed field of the
+ * configuration equals the shape's, unless SF_STEP_GENERIC=1 is set in the environment), -1 = a generic instance
+ * (also: no launch yet, and every launch while the episode log is on). */
+int sf_step_kernel(sf_env *env, int32_t *fixed_shape);
+
 const char *sf_last_error(void);
 int sf_abi_version(void);
 

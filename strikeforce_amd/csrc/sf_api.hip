@@ -1,7 +1,8 @@
 // sf_api.hip — libstrikeforce_amd.so: the gfx950 runtime behind the C-ABI of include/strikeforce.h.
 //
 //   the thin __global__ wrappers around Core<..> (sf_core.hpp): k_reset, k_step, k_step_half <NB, HP, BM, ZL>, one wavefront
-//     per arena (the instance a configuration runs: sf_types.hpp with_variant), k_agent_alive, k_done, k_ep_late, k_replay_fetch
+//     per arena (the instance a configuration runs: sf_types.hpp with_variant), k_step_fixed<Shape> (k_step with a listed
+//     configuration's fields as constants: sf_types.hpp FixedShapes), k_agent_alive, k_done, k_ep_late, k_replay_fetch
 //   k_rank (k_step's launch order) and the episode-log collection kernels k_ep_plan / k_ep_copy
 //   HipRT, the runtime Env<RT> (sf_host.hpp) launches through
 //   Comm, the RCCL exchange of the multi-GPU path
@@ -52,6 +53,23 @@ __global__ __launch_bounds__(64) void k_step(Params p, const uint8_t *cmds, int 
   if (threadIdx.x == 0) sf_diag_times[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
   Core<WaveGfx950, NB, HP, BM, ZL>::template step_body_t<LOG>(lds, p, a, cmds, k);
+#ifdef SF_DIAG_STAMPS
+  __builtin_amdgcn_s_waitcnt(0);  // (the stores have left)
+  if (threadIdx.x == 0) sf_diag_times[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memrealtime();
+#endif
+}
+
+// The throughput kernel of one fixed shape (sf_types.hpp FixedShapes): k_step<SH::NB, false, true, false, false> with the shape's
+// configuration fields as compile-time constants instead of Params reads.  Same source, same results; launched only for
+// an environment whose configuration equals the shape field by field (sf_host.hpp Env::create), with the episode log off.
+template <class SH>
+__global__ __launch_bounds__(64) void k_step_fixed(Params p, const uint8_t *cmds, int k) {
+  extern __shared__ __attribute__((aligned(2048))) uint8_t lds[];  // the RNG power table comes first (W::pow_pair)
+  const int a = p.perm ? (int)gptr(p.perm)[blockIdx.x] : (int)blockIdx.x;
+#ifdef SF_DIAG_STAMPS
+  if (threadIdx.x == 0) sf_diag_times[4 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
+#endif
+  Core<WaveGfx950, SH::NB, false, true, false, SH>::template step_body_t<false>(lds, p, a, cmds, k);
 #ifdef SF_DIAG_STAMPS
   __builtin_amdgcn_s_waitcnt(0);  // (the stores have left)
   if (threadIdx.x == 0) sf_diag_times[4 * blockIdx.x + 3] = __builtin_amdgcn_s_memrealtime();
@@ -274,6 +292,9 @@ struct HipRT {
   }
   // set by the host side while the episode log is on (sf_host.hpp Env::episode_log): k_step's LOG instance is launched
   bool ep_log_on = false;
+  // the fixed shape of the environment's configuration (index in sf_types.hpp FixedShapes; Env::create), -1: none, or
+  // SF_STEP_GENERIC=1.  last_step_shape: what the last step launch ran (sf_step_kernel), -1 = a generic k_step instance
+  int fixed_shape = -1, last_step_shape = -1;
   int launch_step(const Params &p, int NB, const uint8_t *cmds, int k) {
     SF_HIP(hipSetDevice(device));
     std::pair<hipEvent_t, hipEvent_t> *ev = nullptr;
@@ -293,8 +314,17 @@ struct HipRT {
       if (int rc = launch(k_rank, dim3(1), dim3(1024), 0, p, perm)) return rc;
     }
     const bool log = ep_log_on;
-    auto kernel_of = [log](auto v) { return log ? &k_step<v.NB, v.HP, v.BM, v.ZL, true> : &k_step<v.NB, v.HP, v.BM, v.ZL, false>; };
-    if (int rc = launch_arenas(p, NB, kernel_of, cmds, k)) return rc;
+    last_step_shape = log ? -1 : fixed_shape;
+    if (last_step_shape >= 0) {
+      const size_t lds = lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P);  // (an LDS-plane shape: at most 12 KiB of plane, below the 48 KiB default)
+      if (int rc = with_fixed_shape(last_step_shape, FixedShapes{}, SF_ERR_STATE, [&](auto sh) {
+            return launch(&k_step_fixed<decltype(sh)>, dim3((unsigned)p.A), dim3(64), lds, p, cmds, k);
+          }))
+        return rc;
+    } else {
+      auto kernel_of = [log](auto v) { return log ? &k_step<v.NB, v.HP, v.BM, v.ZL, true> : &k_step<v.NB, v.HP, v.BM, v.ZL, false>; };
+      if (int rc = launch_arenas(p, NB, kernel_of, cmds, k)) return rc;
+    }
     if (ev) SF_HIP(hipEventRecord(ev->second, stream));
     return SF_OK;
   }
@@ -748,6 +778,12 @@ int sf_diag_read(sf_env *env, uint32_t *out_host, int32_t arenas) {  // diagnost
              ? SF_OK : SF_ERR_DEVICE;
 }
 #endif
+int sf_step_kernel(sf_env *env, int32_t *fixed_shape) {
+  SF_ENV(env);
+  if (!fixed_shape) return sf::fail(SF_ERR_ARG, "null output");
+  *fixed_shape = env->e.rt.last_step_shape;
+  return SF_OK;
+}
 int sf_kernel_time(sf_env *env, int32_t enable, float *ms, int32_t *launches) {
   SF_ENV(env);
   return env->e.rt.kernel_time(enable, ms, launches);

@@ -38,7 +38,16 @@ enum { LIM_PORTAL = 1000, LIM_BLOCK = 1100 };  // G:37
 // in LDS, [field][slot], and every phase that sweeps them walks 64-slot words — word-major = slot order — up to the
 // highest word in use (Arena::zwn, pwn).  The register form (one lane per slot) is untouched by it: every ZL branch
 // below is `if constexpr`.
-template <class W, int NB, bool HBM_PLANE = false, bool BITMAPS = !HBM_PLANE, bool ZL = false>
+// SH: the shape policy (sf_types.hpp) through which the code reads the configuration fields that never change over an
+// environment's life.  RuntimeShape stands for the Params field; FixedShape<..> returns a compile-time constant, so that the
+// compiler folds the field and every loop-invariant condition derived from it (k_step_fixed, sf_api.hip).
+// SF_SHAPE(f) is field f of `p` under the policy.  A conditional on a constant of the instance, not a plain call of
+// SH::f(p): under RuntimeShape the compiler then sees the expression `p.f` itself and the generic instances come out
+// instruction for instruction as they did before the policy existed.  (The result of a call is `noundef` to the
+// optimiser, a loaded field is not; with the call, loops were unswitched differently on p.mode and p.n_agents, and every
+// generic kernel's register allocation moved.)
+#define SF_SHAPE(f) (SH::FIXED ? SH::f(p) : p.f)
+template <class W, int NB, bool HBM_PLANE = false, bool BITMAPS = !HBM_PLANE, bool ZL = false, class SH = RuntimeShape>
 struct Core {
   using V = typename W::V;
   using P = typename W::P;
@@ -251,10 +260,10 @@ struct Core {
   // cell queries (q wave-uniform)
   static SF_DEV int DX(int d) { return d == 0 ? 1 : (d == 2 ? -1 : 0); }  // wdx CH:47
   static SF_DEV int DY(int d) { return d == 1 ? 1 : (d == 3 ? -1 : 0); }  // wdy
-  static SF_DEV uint32_t cellidx(const Params &p, int f, int r, int c) { return (uint32_t)((f * p.N + r) * p.M + c); }
+  static SF_DEV uint32_t cellidx(const Params &p, int f, int r, int c) { return (uint32_t)((f * SF_SHAPE(N) + r) * SF_SHAPE(M) + c); }
   static SF_DEV uint32_t cellidx_q(const Params &p, uint32_t q) { return cellidx(p, pos_f(q), pos_r(q), pos_c(q)); }
   static SF_DEV bool inmap(const Params &p, int r, int c) {
-    return (uint32_t)r < (uint32_t)p.N && (uint32_t)c < (uint32_t)p.M;
+    return (uint32_t)r < (uint32_t)SF_SHAPE(N) && (uint32_t)c < (uint32_t)SF_SHAPE(M);
   }
   // Out-of-range cells read as indestructible wall (the reference reads without bounds checks in
   // zombie_action / update_bull / portal_damage and relies on border walls).
@@ -335,7 +344,7 @@ struct Core {
   static SF_DEV int b_ind(const Arena &S, const Params &p) {
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      int left = p.B - 64 * j;
+      int left = SF_SHAPE(B) - 64 * j;
       if (left > 0) {
         uint64_t fr = ~W::ballot((S.ba[j] & BA_ALIVE) != 0u) & capmask(left);
         if (fr) return j * 64 + W::ctz64(fr);
@@ -346,12 +355,12 @@ struct Core {
   static SF_DEV int z_ind(const Arena &S, const Params &p) {
     if constexpr (ZL) {
       for (uint32_t j = 0; j < S.zwn; ++j) {
-        const uint64_t fr = ~W::ballot((zl_get(S, ZW_POS, j) & ZF_ALIVE) != 0u) & capmask(p.Z - (int)(64u * j));
+        const uint64_t fr = ~W::ballot((zl_get(S, ZW_POS, j) & ZF_ALIVE) != 0u) & capmask(SF_SHAPE(Z) - (int)(64u * j));
         if (fr) return (int)(64u * j) + W::ctz64(fr);
       }
-      return S.zwn < (uint32_t)zw_for(p.Z) ? (int)(64u * S.zwn) : -1;  // the first slot of a word not in use yet (z_take opens it)
+      return S.zwn < (uint32_t)zw_for(SF_SHAPE(Z)) ? (int)(64u * S.zwn) : -1;  // the first slot of a word not in use yet (z_take opens it)
     }
-    uint64_t fr = ~W::ballot((S.zpos & ZF_ALIVE) != 0u) & capmask(p.Z);
+    uint64_t fr = ~W::ballot((S.zpos & ZF_ALIVE) != 0u) & capmask(SF_SHAPE(Z));
     return fr ? W::ctz64(fr) : -1;
   }
   // ---- the exit table: one lane per exit in registers, or (ZL) pl[slot] in LDS ------------------------------------
@@ -385,7 +394,7 @@ struct Core {
     }
   }
   static SF_DEV int h_ind(const Arena &S, const Params &p) {  // skips `ind` and remote slots
-    uint64_t fr = ~W::ballot((S.hfl & (HF_ALIVE | HF_REMOTE)) != 0u) & capmask(p.H) & ~(1ull << p.ind);
+    uint64_t fr = ~W::ballot((S.hfl & (HF_ALIVE | HF_REMOTE)) != 0u) & capmask(SF_SHAPE(H)) & ~(1ull << SF_SHAPE(ind));
     return fr ? W::ctz64(fr) : -1;
   }
   static SF_DEV int p_ind(const Arena &S, const Params &p) {
@@ -482,7 +491,7 @@ struct Core {
   static SF_DEV uint32_t draw_cell(Arena &S, const uint8_t *lds, const Params &p) {
     uint32_t q = 0u;
     SF_NOUNROLL for (int i = 0; i < 3; ++i) {
-      const uint32_t m = (uint32_t)(i == 0 ? p.F : i == 1 ? p.N : p.M);
+      const uint32_t m = (uint32_t)(i == 0 ? SF_SHAPE(F) : i == 1 ? SF_SHAPE(N) : SF_SHAPE(M));
       q = (q << 10) | (draw(S, lds, p) % m);
     }
     return q;  // ((f << 10) | r) << 10 | c == pos_pack(f, r, c)
@@ -535,7 +544,7 @@ struct Core {
       return;
     }
     SF_PROF(PH_ZOMBIE);
-    const P zalive = ((S.zpos & ZF_ALIVE) != 0u) & W::ltu(W::lane(), (uint32_t)p.Z);
+    const P zalive = ((S.zpos & ZF_ALIVE) != 0u) & W::ltu(W::lane(), (uint32_t)SF_SHAPE(Z));
     uint64_t zm = W::ballot(zalive);
     if (!zm) return;
     const V zq = S.zpos & POS_MASK;
@@ -543,7 +552,7 @@ struct Core {
     // neighbour d of each zombie: packed position and "clear flag byte" bit
     V freebits = V(0u);
     V hnear = V(0u);  // bit d: a human (cell designation s[0]) stands on neighbour d
-    const V ci0 = ((zq >> 20) * (uint32_t)p.N + zr) * (uint32_t)p.M + zc;  // the zombie's own cell index
+    const V ci0 = ((zq >> 20) * (uint32_t)SF_SHAPE(N) + zr) * (uint32_t)SF_SHAPE(M) + zc;  // the zombie's own cell index
     const V qn0 = zq + 1024u, qn1 = zq + 1u, qn2 = zq - 1024u, qn3 = zq - 1u;  // DX/DY order: down, right, up, left
     uint64_t skip = 0ull;
     // the four neighbours' flag bytes first, all four loads in flight at once (with the plane in HBM each is an L2 round
@@ -552,8 +561,8 @@ struct Core {
     P ninb[4];
     for (int d = 0; d < 4; ++d) {
       const V rr = zr + (uint32_t)DX(d), cc = zc + (uint32_t)DY(d);
-      ninb[d] = zalive & W::ltu(rr, (uint32_t)p.N) & W::ltu(cc, (uint32_t)p.M);
-      nfl[d] = W::lds_u8_any(lds, W::select(ninb[d], ci0 + (uint32_t)(DX(d) * p.M + DY(d)), W::select(zalive, ci0, V(0u))));
+      ninb[d] = zalive & W::ltu(rr, (uint32_t)SF_SHAPE(N)) & W::ltu(cc, (uint32_t)SF_SHAPE(M));
+      nfl[d] = W::lds_u8_any(lds, W::select(ninb[d], ci0 + (uint32_t)(DX(d) * SF_SHAPE(M) + DY(d)), W::select(zalive, ci0, V(0u))));
     }
     const bool use_bm = BITMAPS;
     if (use_bm) {
@@ -566,7 +575,7 @@ struct Core {
       skip = W::ballot(zalive & bm_test(S, p, BM_REF, ci0, zalive));
       for (int d = 0; d < 4; ++d) {
         const P inb = ninb[d];
-        const V ci = ci0 + (uint32_t)(DX(d) * p.M + DY(d));
+        const V ci = ci0 + (uint32_t)(DX(d) * SF_SHAPE(M) + DY(d));
         const V fl = nfl[d];
         const P clear = inb & (fl == 0u) & (!bm_test(S, p, BM_REF, ci, inb));
         freebits = freebits | W::select(clear, V(1u << d), V(0u));
@@ -691,21 +700,21 @@ struct Core {
       const V zq = zpw & POS_MASK;
       const V zr = (zq >> 10) & 1023u, zc = zq & 1023u;
       V freebits = V(0u), hnear = V(0u);
-      const V ci0 = ((zq >> 20) * (uint32_t)p.N + zr) * (uint32_t)p.M + zc;
+      const V ci0 = ((zq >> 20) * (uint32_t)SF_SHAPE(N) + zr) * (uint32_t)SF_SHAPE(M) + zc;
       const V qn0 = zq + 1024u, qn1 = zq + 1u, qn2 = zq - 1024u, qn3 = zq - 1u;
       uint64_t skip = 0ull;
       V nfl[4];
       P ninb[4];
       for (int d = 0; d < 4; ++d) {
         const V rr = zr + (uint32_t)DX(d), cc = zc + (uint32_t)DY(d);
-        ninb[d] = zalive & W::ltu(rr, (uint32_t)p.N) & W::ltu(cc, (uint32_t)p.M);
-        nfl[d] = W::lds_u8_any(lds, W::select(ninb[d], ci0 + (uint32_t)(DX(d) * p.M + DY(d)), W::select(zalive, ci0, V(0u))));
+        ninb[d] = zalive & W::ltu(rr, (uint32_t)SF_SHAPE(N)) & W::ltu(cc, (uint32_t)SF_SHAPE(M));
+        nfl[d] = W::lds_u8_any(lds, W::select(ninb[d], ci0 + (uint32_t)(DX(d) * SF_SHAPE(M) + DY(d)), W::select(zalive, ci0, V(0u))));
       }
       if (BITMAPS) {
         skip = W::ballot(zalive & bm_test(S, p, BM_REF, ci0, zalive));
         for (int d = 0; d < 4; ++d) {
           const P inb = ninb[d];
-          const V ci = ci0 + (uint32_t)(DX(d) * p.M + DY(d));
+          const V ci = ci0 + (uint32_t)(DX(d) * SF_SHAPE(M) + DY(d));
           const P clear = inb & (nfl[d] == 0u) & (!bm_test(S, p, BM_REF, ci, inb));
           freebits = freebits | W::select(clear, V(1u << d), V(0u));
           hnear = hnear | W::select(inb & bm_test(S, p, BM_HUM, ci, inb), V(1u << d), V(0u));
@@ -778,7 +787,7 @@ struct Core {
     if (BITMAPS) {
       bm_clear(S, p, BM_HUM, hci, hocc);
       // (the punches above have designated new bullets and orphaned old ones: the whole bitmap, not the present bullets' words)
-      W::lds_zero(S.bm + BM_REF * p.bm_words, (uint32_t)p.bm_words);
+      W::lds_zero(S.bm + BM_REF * SF_SHAPE(bm_words), (uint32_t)SF_SHAPE(bm_words));
     }
   }
 
@@ -884,7 +893,7 @@ struct Core {
     if (built) {
       bm_clear(S, p, BM_HUM, hci, hocc);
       bm_zombies_zl(S, p, BM_ZOM, false);
-      W::lds_zero(S.bm + BM_REF * p.bm_words, (uint32_t)p.bm_words);  // (the radiation bullets took over their cells' designation)
+      W::lds_zero(S.bm + BM_REF * SF_SHAPE(bm_words), (uint32_t)SF_SHAPE(bm_words));  // (the radiation bullets took over their cells' designation)
     }
   }
 
@@ -897,10 +906,10 @@ struct Core {
     const int sit = showit_q(S, lds, p, q, fl);
     if (!(fl & SF_CELL_TEMP)) return;
     const uint32_t ci = cellidx_q(p, q);
-    int32_t *dmg = p.aux_dmg + (size_t)a * (size_t)p.cells;
+    int32_t *dmg = p.aux_dmg + (size_t)a * (size_t)SF_SHAPE(cells);
     const int32_t d = W::uload_i32(dmg + ci);
     if (sit == SH_PUP && d >= LIM_PORTAL) {
-      const int i = (int)W::uload_i16(p.aux_pidx + (size_t)a * (size_t)p.cells + ci);
+      const int i = (int)W::uload_i16(p.aux_pidx + (size_t)a * (size_t)SF_SHAPE(cells) + ci);
       const uint32_t e1 = p_read(S, (uint32_t)i) & POS_MASK;
       const uint32_t c1 = cellidx_q(p, e1);
       W::ulds_store_u8(lds, c1, W::ulds_u8(lds, c1) & ~(uint32_t)(SF_CELL_POUT | SF_CELL_TEMP));
@@ -928,13 +937,13 @@ struct Core {
     for (int j = 0; j < NB; ++j) {
       const P alive = (S.ba[j] & BA_ALIVE) != 0u;
       cell[j] = S.ba[j] & POS_MASK;
-      const V ci = ((cell[j] >> 20) * (uint32_t)p.N + ((cell[j] >> 10) & 1023u)) * (uint32_t)p.M + (cell[j] & 1023u);
+      const V ci = ((cell[j] >> 20) * (uint32_t)SF_SHAPE(N) + ((cell[j] >> 10) & 1023u)) * (uint32_t)SF_SHAPE(M) + (cell[j] & 1023u);
       const V fl = W::lds_u8(lds, ci, alive);
       cand[j] = W::ballot(alive & ((fl & SF_CELL_TEMP) != 0u) & ((fl & (SF_CELL_WALL | SF_CELL_PIN_UP)) != 0u));
       any = any || cand[j] != 0ull;
     }
     if (!any) return;
-    int32_t *dmg = p.aux_dmg + (size_t)a * (size_t)p.cells;
+    int32_t *dmg = p.aux_dmg + (size_t)a * (size_t)SF_SHAPE(cells);
     // pass 1, slot order: absorb.  `s[2] = 0` un-designates the cell's bullet; every bullet standing on
     // this cell is absorbed by this same loop, so clearing each absorbed bullet's own flags is equivalent.
 #pragma unroll
@@ -976,21 +985,21 @@ struct Core {
   // bracket.  Maps whose bitmaps would not fit (256 x 256) keep the ballot loops (BITMAPS false).
   enum { BM_HUM = 0, BM_ZOM = 1, BM_REF = 2 };
   static SF_DEV V cell_index_v(const Params &p, const V &q) {  // packed position (flag bits above it ignored) -> cell
-    return W::mad24(W::mad24((q >> 20) & 3u, (uint32_t)p.N, (q >> 10) & 1023u), (uint32_t)p.M, q & 1023u);
+    return W::mad24(W::mad24((q >> 20) & 3u, (uint32_t)SF_SHAPE(N), (q >> 10) & 1023u), (uint32_t)SF_SHAPE(M), q & 1023u);
   }
   static SF_DEV void bm_set(Arena &S, const Params &p, int which, const V &ci, P pred) {
-    W::lds_or_u32(S.bm + which * p.bm_words, ci >> 5, W::shlv(V(1u), ci & 31u), pred);
+    W::lds_or_u32(S.bm + which * SF_SHAPE(bm_words), ci >> 5, W::shlv(V(1u), ci & 31u), pred);
   }
   static SF_DEV void bm_clear(Arena &S, const Params &p, int which, const V &ci, P pred) {
-    W::lds_store_u32(S.bm + which * p.bm_words, ci >> 5, V(0u), pred);
+    W::lds_store_u32(S.bm + which * SF_SHAPE(bm_words), ci >> 5, V(0u), pred);
   }
   static SF_DEV P bm_test(const Arena &S, const Params &p, int which, const V &ci, P pred) {
-    return (W::shrv(W::lds_u32(S.bm + which * p.bm_words, ci >> 5, pred), ci & 31u) & 1u) != 0u;
+    return (W::shrv(W::lds_u32(S.bm + which * SF_SHAPE(bm_words), ci >> 5, pred), ci & 31u) & 1u) != 0u;
   }
   // set bit, telling whether it was set already (by an earlier build or by another lane of this very call)
   static SF_DEV P bm_claim(Arena &S, const Params &p, int which, const V &ci, P pred) {
     const V bit = W::shlv(V(1u), ci & 31u);
-    return pred & ((W::lds_or_rtn_u32(S.bm + which * p.bm_words, ci >> 5, bit, pred) & bit) != 0u);
+    return pred & ((W::lds_or_rtn_u32(S.bm + which * SF_SHAPE(bm_words), ci >> 5, bit, pred) & bit) != 0u);
   }
   static SF_DEV void bm_bullets(Arena &S, const Params &p, int which, bool set) {  // the designated bullets' cells
 #pragma unroll
@@ -1048,10 +1057,10 @@ struct Core {
         add_lane(S.hef, (uint32_t)(owner - 1), eff);
       }
       if (hp <= 0) {
-        W::setlane(S.hfl, (uint32_t)hv, hv == p.ind ? (vfl & ~HF_ALIVE) : (vfl & ~(HF_ALIVE | HF_CTRL | HF_OCC)));
+        W::setlane(S.hfl, (uint32_t)hv, hv == SF_SHAPE(ind) ? (vfl & ~HF_ALIVE) : (vfl & ~(HF_ALIVE | HF_CTRL | HF_OCC)));
         if (owner && owner_team == my_team && vteam != my_team) {
           ++S.tkills, S.loot += 100;
-          if (owner == p.ind + 1) S.loot += 900, ++S.kills;
+          if (owner == SF_SHAPE(ind) + 1) S.loot += 900, ++S.kills;
         }
         if (cross) add_lane(S.hk, (uint32_t)(owner - 1), 1);
       }
@@ -1069,7 +1078,7 @@ struct Core {
         if (owner && owner_team == my_team) {
           const int pts = 500 + ((zp & ZF_SUPER) ? 250 : 0);
           ++S.tkills, S.loot += pts / 10;
-          if (owner == p.ind + 1) S.loot += pts * 9 / 10, ++S.kills;
+          if (owner == SF_SHAPE(ind) + 1) S.loot += pts * 9 / 10, ++S.kills;
         }
         if (owner) add_lane(S.hk, (uint32_t)(owner - 1), 1);
       }
@@ -1080,9 +1089,9 @@ struct Core {
     {
       const P dying = ((S.hfl & HF_ALIVE) != 0u) & W::le0(S.hhp);                  // G:641-645
       // s[0] = (human == &hum[ind]); deleteAgent() only for i != ind  G:643,648-649
-      S.hfl = W::select(dying, W::select(W::lane() == (uint32_t)p.ind, S.hfl & ~HF_ALIVE, S.hfl & ~(HF_ALIVE | HF_CTRL | HF_OCC)), S.hfl);
+      S.hfl = W::select(dying, W::select(W::lane() == (uint32_t)SF_SHAPE(ind), S.hfl & ~HF_ALIVE, S.hfl & ~(HF_ALIVE | HF_CTRL | HF_OCC)), S.hfl);
     }
-    const uint32_t my_team = (uint32_t)h_team(W::readlane(S.hfl, (uint32_t)p.ind));
+    const uint32_t my_team = (uint32_t)h_team(W::readlane(S.hfl, (uint32_t)SF_SHAPE(ind)));
     if (BITMAPS) {
       // who stands on a designated bullet: the bullets scatter their cells, the characters test their own
       bool any = false;
@@ -1111,7 +1120,7 @@ struct Core {
             if (slot >= 0) hit_one(S, p, my_team, slot, -1, (int)(64u * j + i));
           }
         }
-        W::lds_zero(S.bm + BM_REF * p.bm_words, (uint32_t)p.bm_words);
+        W::lds_zero(S.bm + BM_REF * SF_SHAPE(bm_words), (uint32_t)SF_SHAPE(bm_words));
         return;
       }
       {
@@ -1171,8 +1180,8 @@ struct Core {
       const V d = (S.ba[j] >> BA_WAY_SH) & 3u;
       const V rr = ((q >> 10) & 1023u) + W::select(d == 0u, V(1u), W::select(d == 2u, V(0xffffffffu), V(0u)));
       const V cc = (q & 1023u) + W::select(d == 1u, V(1u), W::select(d == 3u, V(0xffffffffu), V(0u)));
-      const P inb = live & W::ltu(rr, (uint32_t)p.N) & W::ltu(cc, (uint32_t)p.M);
-      const V ci = ((q >> 20) * (uint32_t)p.N + rr) * (uint32_t)p.M + cc;
+      const P inb = live & W::ltu(rr, (uint32_t)SF_SHAPE(N)) & W::ltu(cc, (uint32_t)SF_SHAPE(M));
+      const V ci = ((q >> 20) * (uint32_t)SF_SHAPE(N) + rr) * (uint32_t)SF_SHAPE(M) + cc;
       const V fl = W::lds_u8(lds, ci, inb);
       const P temp = (fl & SF_CELL_TEMP) != 0u, wall = (fl & SF_CELL_WALL) != 0u,
               pin = (fl & (SF_CELL_PIN_UP | SF_CELL_PIN_DN)) != 0u;
@@ -1261,7 +1270,7 @@ struct Core {
     const uint32_t ci = cellidx_q(p, q);
     const uint32_t fl = W::ulds_u8(lds, ci);
     if (!(fl & (SF_CELL_PIN_UP | SF_CELL_PIN_DN))) return;  // portal_ind == -1
-    const int index = (fl & SF_CELL_TEMP) ? (int)W::uload_i16(p.aux_pidx + (size_t)a * (size_t)p.cells + ci)
+    const int index = (fl & SF_CELL_TEMP) ? (int)W::uload_i16(p.aux_pidx + (size_t)a * (size_t)SF_SHAPE(cells) + ci)
                                           : (int)W::uload_i16(p.map_pidx + ci);
     if (index < 0 || index >= p.P) return;
     const uint32_t e = p_read(S, (uint32_t)index) & POS_MASK;
@@ -1291,7 +1300,7 @@ struct Core {
       const uint32_t bp = W::readlane(S.hbpk, i);
       const uint32_t blocks = bp & 255u, portals = (bp >> 8) & 255u;
       const int pind = (int)((bp >> 16) & 255u) - 1;
-      int32_t *dmg = p.aux_dmg + (size_t)a * (size_t)p.cells;
+      int32_t *dmg = p.aux_dmg + (size_t)a * (size_t)SF_SHAPE(cells);
       if (c == '[') {
         if (blocks) {
           W::ulds_store_u8(lds, ci, fl | SF_CELL_TEMP | SF_CELL_WALL);
@@ -1304,7 +1313,7 @@ struct Core {
       if (pind != -1) {
         W::ulds_store_u8(lds, ci, fl | SF_CELL_TEMP | SF_CELL_PIN_UP);
         W::ustore_i32(dmg + ci, 0);
-        W::ustore_i16(p.aux_pidx + (size_t)a * (size_t)p.cells + ci, (int16_t)pind);
+        W::ustore_i16(p.aux_pidx + (size_t)a * (size_t)SF_SHAPE(cells) + ci, (int16_t)pind);
         W::setlane(S.hbpk, i, bp & 0xffffu);
         S.dirty = 1u;
       } else if (portals) {
@@ -1473,12 +1482,12 @@ struct Core {
 
   static SF_DEV void human_action(Arena &S, uint8_t *lds, const Params &p, int a) {
     SF_PROF(PH_HUMAN);
-    const uint64_t alive = W::ballot((S.hfl & HF_ALIVE) != 0u) & capmask(p.H);
+    const uint64_t alive = W::ballot((S.hfl & HF_ALIVE) != 0u) & capmask(SF_SHAPE(H));
     // get_command G:929-937, slot order, for i != ind: remote keep theirs, rnpc draw, agents keep theirs, others '+'
     {
-      const P ext = ((S.hfl & (HF_REMOTE | HF_CTRL)) != 0u) | (W::lane() == (uint32_t)p.ind);
+      const P ext = ((S.hfl & (HF_REMOTE | HF_CTRL)) != 0u) | (W::lane() == (uint32_t)SF_SHAPE(ind));
       S.hcmd = W::select(ext, S.hcmd, V((uint32_t)'+'));
-      uint64_t m = alive & ~(1ull << p.ind) & W::ballot((S.hfl & (HF_RNPC | HF_REMOTE)) == HF_RNPC);
+      uint64_t m = alive & ~(1ull << SF_SHAPE(ind)) & W::ballot((S.hfl & (HF_RNPC | HF_REMOTE)) == HF_RNPC);
       const bool pick_weapon = m && S.frame % 50 <= 1;  // the same for every NPC of this sweep
       while (m) {
         const uint32_t i = (uint32_t)W::ctz64(m);
@@ -1511,10 +1520,10 @@ struct Core {
     const V dir = W::select(is_move, prm, way - 1u);
     const V rr = hr + W::select(dir == 0u, V(1u), W::select(dir == 2u, V(0xffffffffu), V(0u)));
     const V cc = hc + W::select(dir == 1u, V(1u), W::select(dir == 3u, V(0xffffffffu), V(0u)));
-    const P inb = (is_move | is_place | is_shoot) & W::ltu(rr, (uint32_t)p.N) & W::ltu(cc, (uint32_t)p.M);
+    const P inb = (is_move | is_place | is_shoot) & W::ltu(rr, (uint32_t)SF_SHAPE(N)) & W::ltu(cc, (uint32_t)SF_SHAPE(M));
     const V tq = (q0 & (3u << 20)) | (rr << 10) | cc;
-    const V oci = (hf * (uint32_t)p.N + hr) * (uint32_t)p.M + hc;
-    const V tci = (hf * (uint32_t)p.N + rr) * (uint32_t)p.M + cc;
+    const V oci = (hf * (uint32_t)SF_SHAPE(N) + hr) * (uint32_t)SF_SHAPE(M) + hc;
+    const V tci = (hf * (uint32_t)SF_SHAPE(N) + rr) * (uint32_t)SF_SHAPE(M) + cc;
     const V tfl = W::lds_u8(lds, tci, inb);
     const V ofl = W::lds_u8(lds, oci, live);
     // who is on the target cells; do two humans meet on a cell
@@ -1577,7 +1586,7 @@ struct Core {
       int freeb = 0;
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
-        const int left = p.B - 64 * j;
+        const int left = SF_SHAPE(B) - 64 * j;
         if (left > 0) freeb += W::popc64(~W::ballot((S.ba[j] & BA_ALIVE) != 0u) & capmask(left));
       }
       if (freeb < W::popc64(shooters)) slow = true;
@@ -1713,15 +1722,15 @@ struct Core {
     return W::ballot(((S.hfl & HF_ALIVE) != 0u) & (team != 0u) & (team != my_team)) == 0ull;
   }
   static SF_DEV int check_end(const Arena &S, const Params &p) {
-    const uint32_t my_team = (uint32_t)h_team(W::readlane(S.hfl, (uint32_t)p.ind));
-    if (p.mode == SF_MODE_BATTLE && rivals_are_dead(S, my_team)) return SF_WON;
-    if ((int32_t)W::readlane(S.hhp, (uint32_t)p.ind) <= 0) return SF_DIED;
-    if (p.mode == SF_MODE_TIMER) {
-      if (S.frame - 1 >= p.timer_lim) return S.kills < p.level * 5 ? SF_TIME_LOST : SF_TIME_WON;
+    const uint32_t my_team = (uint32_t)h_team(W::readlane(S.hfl, (uint32_t)SF_SHAPE(ind)));
+    if (SF_SHAPE(mode) == SF_MODE_BATTLE && rivals_are_dead(S, my_team)) return SF_WON;
+    if ((int32_t)W::readlane(S.hhp, (uint32_t)SF_SHAPE(ind)) <= 0) return SF_DIED;
+    if (SF_SHAPE(mode) == SF_MODE_TIMER) {
+      if (S.frame - 1 >= p.timer_lim) return S.kills < SF_SHAPE(level) * 5 ? SF_TIME_LOST : SF_TIME_WON;
       return SF_RUNNING;
     }
-    if (p.level * 5 <= S.kills && p.mode == SF_MODE_SOLO) return SF_WON;
-    if (p.level * 10 <= S.tkills && rivals_are_dead(S, my_team) && p.mode == SF_MODE_SQUAD) return SF_WON;
+    if (SF_SHAPE(level) * 5 <= S.kills && SF_SHAPE(mode) == SF_MODE_SOLO) return SF_WON;
+    if (SF_SHAPE(level) * 10 <= S.tkills && rivals_are_dead(S, my_team) && SF_SHAPE(mode) == SF_MODE_SQUAD) return SF_WON;
     return SF_RUNNING;
   }
 
@@ -1730,8 +1739,8 @@ struct Core {
   template <bool LOG>
   static SF_DEV void latch_results(const Arena &S, const Params &p, int a) {
     // [kills, teams_kills, loot, damage, effect, Hp, frames, outcome] per agent
-    const P ag = W::ltu(W::lane(), (uint32_t)p.n_agents);
-    const V base = (V((uint32_t)a * (uint32_t)p.n_agents) + W::lane()) * 8u;
+    const P ag = W::ltu(W::lane(), (uint32_t)SF_SHAPE(n_agents));
+    const V base = (V((uint32_t)a * (uint32_t)SF_SHAPE(n_agents)) + W::lane()) * 8u;
     uint32_t *res = (uint32_t *)p.results;
     W::gstore(res, base + 0u, S.hk, ag);
     W::gstore(res, base + 1u, V((uint32_t)S.tkills), ag);
@@ -1748,7 +1757,7 @@ struct Core {
     uint32_t *const ring = p.tab->ep_ring;
     if (ring) {
       // (word index in 32 bits: sf_episode_log keeps the ring below 2^31 words)
-      const uint32_t depth = (uint32_t)p.tab->ep_depth, rw = (uint32_t)ep_record_words(p.n_agents);
+      const uint32_t depth = (uint32_t)p.tab->ep_depth, rw = (uint32_t)ep_record_words(SF_SHAPE(n_agents));
       const V r = V(((uint32_t)a * depth + ((uint32_t)S.episodes & (depth - 1u))) * rw);
       V h = V((uint32_t)a);
       W::setlane(h, 1u, (uint32_t)S.episodes);
@@ -1779,7 +1788,7 @@ struct Core {
     uint32_t *const ring = p.tab->ep_ring;
     const int32_t *sc = p.scal + (size_t)a * SC_WORDS;
     if (!ring) return;
-    const uint32_t depth = (uint32_t)p.tab->ep_depth, rw = (uint32_t)ep_record_words(p.n_agents);
+    const uint32_t depth = (uint32_t)p.tab->ep_depth, rw = (uint32_t)ep_record_words(SF_SHAPE(n_agents));
     if (after_reset) {
       const uint32_t n = depth * rw;
       for (uint32_t i = 0u; i < n; i += 64u)
@@ -1789,8 +1798,8 @@ struct Core {
     if (!W::uload_i32(sc + SC_ENDED)) return;
     const uint32_t ep = (uint32_t)W::uload_i32(sc + SC_EPISODES) - 1u;
     uint64_t tb = ((uint64_t)(uint32_t)W::uload_i32(sc + SC_TB_HI) << 32) | (uint32_t)W::uload_i32(sc + SC_TB_LO);
-    if (p.auto_reset) tb -= (uint64_t)(uint32_t)p.reseed;
-    const uint32_t *res = (const uint32_t *)p.results + (size_t)a * (size_t)p.n_agents * 8u;
+    if (SF_SHAPE(auto_reset)) tb -= (uint64_t)(uint32_t)p.reseed;
+    const uint32_t *res = (const uint32_t *)p.results + (size_t)a * (size_t)SF_SHAPE(n_agents) * 8u;
     const uint32_t frame = (uint32_t)W::uload_i32((const int32_t *)res + 6), outcome = (uint32_t)W::uload_i32((const int32_t *)res + 7);
     V h = V((uint32_t)a);
     W::setlane(h, 1u, ep);
@@ -1799,7 +1808,7 @@ struct Core {
     W::setlane(h, 6u, (frame - 1u) / 2u), W::setlane(h, 7u, outcome);
     const V r = V(((uint32_t)a * depth + (ep & (depth - 1u))) * rw);
     W::gstore(ring, r + W::lane(), h, W::ltu(W::lane(), (uint32_t)EP_HDR_WORDS));
-    const uint32_t n = 8u * (uint32_t)p.n_agents;
+    const uint32_t n = 8u * (uint32_t)SF_SHAPE(n_agents);
     for (uint32_t i = 0u; i < n; i += 64u) {
       const P in = W::ltu(W::lane() + i, n);
       W::gstore(ring, r + (uint32_t)EP_HDR_WORDS + W::lane() + i, W::gload(res, W::lane() + i, in), in);
@@ -1827,9 +1836,9 @@ struct Core {
     const uint32_t o0 = (uint32_t)W::uload_i32((const int32_t *)r.off + a), o1 = (uint32_t)W::uload_i32((const int32_t *)r.off + a + 1);
     const uint32_t len = o1 - o0;
     const int32_t done = W::uload_i32(sc + SC_DONE);
-    const P ag = W::ltu(W::lane(), (uint32_t)p.n_agents);
-    const V row = W::lane() + (uint32_t)a * (uint32_t)p.n_agents;
-    const P me = W::lane() == (uint32_t)p.ind;
+    const P ag = W::ltu(W::lane(), (uint32_t)SF_SHAPE(n_agents));
+    const V row = W::lane() + (uint32_t)a * (uint32_t)SF_SHAPE(n_agents);
+    const P me = W::lane() == (uint32_t)SF_SHAPE(ind);
     if (mode == 0) {
       bool go = false;
       if (state == SF_REPLAY_RUNNING && done) {
@@ -1853,7 +1862,7 @@ struct Core {
       return;
     }
     if (state != SF_REPLAY_RUNNING || done) return;  // only an arena that took the line of `ind` at this loop top
-    const V fl = W::gload(p.hum, W::lane() + ((uint32_t)HW_FLAGS * (uint32_t)p.A + (uint32_t)a) * (uint32_t)p.H, ag);
+    const V fl = W::gload(p.hum, W::lane() + ((uint32_t)HW_FLAGS * (uint32_t)p.A + (uint32_t)a) * (uint32_t)SF_SHAPE(H), ag);
     const P takes = ag & !me & ((fl & (HF_ALIVE | HF_CTRL)) == (HF_ALIVE | HF_CTRL));
     const uint64_t bal = W::ballot(takes);
     const V line = V(cur) + W::rank_below(bal);
@@ -1903,7 +1912,7 @@ struct Core {
     } else {
       S.ppos = W::gload(p.map_exits, W::lane(), W::ltu(W::lane(), (uint32_t)p.P));
     }
-    W::copy_g2l(lds, p.map_flags, (uint32_t)p.cells_pad);
+    W::copy_g2l(lds, p.map_flags, (uint32_t)SF_SHAPE(cells_pad));
     S.dirty = 1u;
     if (adopt) {
       prewarm(S, lds, p, 1024u);  // whatever is still missing
@@ -1912,7 +1921,7 @@ struct Core {
     } else {
       srand_(S, lds, p, tb, serial);
     }
-    if (p.auto_reset) {  // arm the warm-up of the episode after this one
+    if (SF_SHAPE(auto_reset)) {  // arm the warm-up of the episode after this one
       seed_digits(S.rseed2, tb + (uint64_t)(uint32_t)p.reseed, 1u);
       S.rl2 = V(RL_ZERO);
       S.warm = 0u, S.la2_ok = 0u;
@@ -1920,24 +1929,24 @@ struct Core {
     // load_data(): who stands where.  Solo/Timer: the player at (0,1,1) (G:1905-1920).  Squad: the player at (0,3,1),
     // four team-mates at (0,1,2..5), five opponents at (squad_floor,1,6..10), all built from the NPC record
     // (G:1861-1903).  Battle: every commanded human, placed below on random '.' cells (G:1846-1859).
-    const int count = p.mode == SF_MODE_BATTLE ? p.n_agents : (p.mode == SF_MODE_SQUAD ? 10 : 1);
+    const int count = SF_SHAPE(mode) == SF_MODE_BATTLE ? SF_SHAPE(n_agents) : (SF_SHAPE(mode) == SF_MODE_SQUAD ? 10 : 1);
     SF_NOUNROLL for (int i = 0; i < count; ++i) {
       int prof = 0, team = 1;
       uint32_t q = pos_pack(0, 1, 1), fl = HF_CTRL;
-      if (p.mode == SF_MODE_BATTLE) {
-        q = POS_NONE, team = p.tab->teams[i], fl = HF_CTRL | (i != p.ind ? HF_REMOTE : 0u);
-      } else if (p.mode == SF_MODE_SQUAD) {
+      if (SF_SHAPE(mode) == SF_MODE_BATTLE) {
+        q = POS_NONE, team = p.tab->teams[i], fl = HF_CTRL | (i != SF_SHAPE(ind) ? HF_REMOTE : 0u);
+      } else if (SF_SHAPE(mode) == SF_MODE_SQUAD) {
         prof = i ? 1 : 0;
         team = i < 5 ? 1 : 2;
         q = i == 0 ? pos_pack(0, 3, 1) : pos_pack(i < 5 ? 0 : p.squad_floor, 1, i + 1);
-        fl = (i == 0 || i < p.n_agents) ? HF_CTRL : 0u;  // USE_AGENT_IN_SQUAD_NPCS G:1883-1885
+        fl = (i == 0 || i < SF_SHAPE(n_agents)) ? HF_CTRL : 0u;  // USE_AGENT_IN_SQUAD_NPCS G:1883-1885
       }
       // every commanded human of a Battle match is built from its own record when the match brought them
-      human_make(S, p, (uint32_t)i, prof, q, 1, team, fl, (p.mode == SF_MODE_BATTLE && p.npc_block > 1) ? i : 0);
+      human_make(S, p, (uint32_t)i, prof, q, 1, team, fl, (SF_SHAPE(mode) == SF_MODE_BATTLE && p.npc_block > 1) ? i : 0);
     }
-    if (p.mode == SF_MODE_BATTLE) {
+    if (SF_SHAPE(mode) == SF_MODE_BATTLE) {
       S.hfl = S.hfl & ~HF_OCC;  // not on the map until placed
-      SF_NOUNROLL for (int i = 0; i < p.n_agents; ++i) {
+      SF_NOUNROLL for (int i = 0; i < SF_SHAPE(n_agents); ++i) {
         const uint32_t way = draw(S, lds, p) % 4u + 1u;
         SF_NOUNROLL for (int guard = 0; guard < (1 << 20); ++guard) {  // `while(true)` with an exit every wave reaches
           const uint32_t q = draw_cell(S, lds, p);
@@ -1976,14 +1985,14 @@ struct Core {
         portal_damage(S, lds, p);
         SF_STAMP(S, 2);
       }
-      if (p.auto_reset) prewarm(S, lds, p, S.wrate);  // warm-up draws of the next episode, spread over the step so that
+      if (SF_SHAPE(auto_reset)) prewarm(S, lds, p, S.wrate);  // warm-up draws of the next episode, spread over the step so that
       SF_STAMP(S, 4);
       update_tmp(S, lds, p, a);             // each one's table lookup is in flight while the tick goes on
       SF_STAMP(S, 5);
       hits(S, p);
       SF_STAMP(S, 6);
       ++S.frame;  // updmap G:489-495 clears render-only bits
-      if (p.auto_reset) prewarm(S, lds, p, S.wrate);
+      if (SF_SHAPE(auto_reset)) prewarm(S, lds, p, S.wrate);
       SF_STAMP(S, 4);
       const uint32_t j2 = S.jomle;
       update_bull(S, lds, p);
@@ -2005,7 +2014,7 @@ struct Core {
       if (!S.done || pass == 1) break;
       if (S.ended < 255) ++S.ended;  // episodes that ended during this launch (sf_done with auto_reset)
       ++S.episodes;
-      if (!p.auto_reset) break;
+      if (!SF_SHAPE(auto_reset)) break;
       const uint64_t tb = (((uint64_t)S.tb_hi << 32) | S.tb_lo) + (uint64_t)(uint32_t)p.reseed;
       const uint64_t sr = ((uint64_t)S.sr_hi << 32) | S.sr_lo;
       const int32_t ep = S.episodes;
@@ -2021,10 +2030,10 @@ struct Core {
   // copy_plane = false: the caller has the flag plane's loads in flight already (step_body) and stores them itself
   static SF_DEV void load(Arena &S, uint8_t *lds, const Params &p, int a, bool copy_plane = true) {
     const V ln = W::lane();
-    const size_t AH = (size_t)p.A * (size_t)p.H, AZ = (size_t)p.A * (size_t)p.Z, AB = (size_t)p.A * (size_t)p.B;
+    const size_t AH = (size_t)p.A * (size_t)SF_SHAPE(H), AZ = (size_t)p.A * (size_t)SF_SHAPE(Z), AB = (size_t)p.A * (size_t)SF_SHAPE(B);
     {
-      const P in = W::ltu(ln, (uint32_t)p.H);
-      const uint32_t *h = p.hum + (size_t)a * (size_t)p.H;
+      const P in = W::ltu(ln, (uint32_t)SF_SHAPE(H));
+      const uint32_t *h = p.hum + (size_t)a * (size_t)SF_SHAPE(H);
       S.hpos = W::gload(h + HW_POS * AH, ln, in), S.hfl = W::gload(h + HW_FLAGS * AH, ln, in);
       S.hhp = W::gload(h + HW_HP * AH, ln, in), S.hst = W::gload(h + HW_STAMINA * AH, ln, in);
       S.hmd = W::gload(h + HW_MINDAMAGE * AH, ln, in), S.hk = W::gload(h + HW_KILLS * AH, ln, in);
@@ -2036,28 +2045,28 @@ struct Core {
     }
     if constexpr (ZL) {
       S.zpos = V(0u), S.zhp = V(0u), S.zmd = V(0u);
-      const uint32_t *z = p.zom + (size_t)a * (size_t)p.Z;
+      const uint32_t *z = p.zom + (size_t)a * (size_t)SF_SHAPE(Z);
       S.zwn = (uint32_t)W::uload_i32(p.scal + (size_t)a * SC_WORDS + SC_ZWN);
-      if (S.zwn > (uint32_t)zw_for(p.Z)) S.zwn = (uint32_t)zw_for(p.Z);
+      if (S.zwn > (uint32_t)zw_for(SF_SHAPE(Z))) S.zwn = (uint32_t)zw_for(SF_SHAPE(Z));
       S.zwhi = S.zwn;
       for (uint32_t j = 0; j < S.zwn; ++j) {
         const V sl = ln + 64u * j;
-        const P in = W::ltu(sl, (uint32_t)p.Z);
+        const P in = W::ltu(sl, (uint32_t)SF_SHAPE(Z));
         zl_put(S, ZW_POS, j, W::gload(z + ZW_POS * AZ, sl, in), W::all());
         zl_put(S, ZW_HP, j, W::gload(z + ZW_HP * AZ, sl, in), W::all());
         zl_put(S, ZW_MINDAMAGE, j, W::gload(z + ZW_MINDAMAGE * AZ, sl, in), W::all());
       }
     } else {
-      const P in = W::ltu(ln, (uint32_t)p.Z);
-      const uint32_t *z = p.zom + (size_t)a * (size_t)p.Z;
+      const P in = W::ltu(ln, (uint32_t)SF_SHAPE(Z));
+      const uint32_t *z = p.zom + (size_t)a * (size_t)SF_SHAPE(Z);
       S.zpos = W::gload(z + ZW_POS * AZ, ln, in), S.zhp = W::gload(z + ZW_HP * AZ, ln, in);
       S.zmd = W::gload(z + ZW_MINDAMAGE * AZ, ln, in);
     }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const V sl = ln + (uint32_t)(64 * j);
-      const P in = W::ltu(sl, (uint32_t)p.B);
-      const uint32_t *b = p.bul + (size_t)a * (size_t)p.B;
+      const P in = W::ltu(sl, (uint32_t)SF_SHAPE(B));
+      const uint32_t *b = p.bul + (size_t)a * (size_t)SF_SHAPE(B);
       S.ba[j] = W::gload(b + BW_A * AB, sl, in), S.bd[j] = W::gload(b + BW_DAMAGE * AB, sl, in);
       S.bb[j] = W::gload(b + BW_B * AB, sl, in), S.bc[j] = W::gload(b + BW_C * AB, sl, in);
     }
@@ -2095,17 +2104,17 @@ struct Core {
     S.sr_lo = W::readlane(sc, SC_SR_LO), S.sr_hi = W::readlane(sc, SC_SR_HI);
     S.warm = W::readlane(sc, SC_WARM);
     S.pd01 = W::readlane(sc, SC_PD01), S.pd23 = W::readlane(sc, SC_PD23), S.pd45 = W::readlane(sc, SC_PD45);
-    if (!HBM_PLANE && copy_plane) W::copy_g2l(lds, p.flags + (size_t)a * (size_t)p.cells_pad, (uint32_t)p.cells_pad);
+    if (!HBM_PLANE && copy_plane) W::copy_g2l(lds, p.flags + (size_t)a * (size_t)SF_SHAPE(cells_pad), (uint32_t)SF_SHAPE(cells_pad));
     S.dirty = 0u;
     if (copy_plane) draw_issue(S, p);  // the lookup of the next draw (S.la) is not part of the stored state
   }
 
   static SF_DEV void store(const Arena &S, const uint8_t *lds, const Params &p, int a) {
     const V ln = W::lane();
-    const size_t AH = (size_t)p.A * (size_t)p.H, AZ = (size_t)p.A * (size_t)p.Z, AB = (size_t)p.A * (size_t)p.B;
+    const size_t AH = (size_t)p.A * (size_t)SF_SHAPE(H), AZ = (size_t)p.A * (size_t)SF_SHAPE(Z), AB = (size_t)p.A * (size_t)SF_SHAPE(B);
     {
-      const P in = W::ltu(ln, (uint32_t)p.H);
-      uint32_t *h = p.hum + (size_t)a * (size_t)p.H;
+      const P in = W::ltu(ln, (uint32_t)SF_SHAPE(H));
+      uint32_t *h = p.hum + (size_t)a * (size_t)SF_SHAPE(H);
       W::gstore(h + HW_POS * AH, ln, S.hpos, in), W::gstore(h + HW_FLAGS * AH, ln, S.hfl, in);
       W::gstore(h + HW_HP * AH, ln, S.hhp, in), W::gstore(h + HW_STAMINA * AH, ln, S.hst, in);
       W::gstore(h + HW_MINDAMAGE * AH, ln, S.hmd, in), W::gstore(h + HW_KILLS * AH, ln, S.hk, in);
@@ -2117,10 +2126,10 @@ struct Core {
     uint32_t zlive_n = 0u;
     (void)zlive_n;
     if constexpr (ZL) {
-      uint32_t *z = p.zom + (size_t)a * (size_t)p.Z;
+      uint32_t *z = p.zom + (size_t)a * (size_t)SF_SHAPE(Z);
       for (uint32_t j = 0; j < S.zwhi; ++j) {  // words an earlier episode of this launch had in use are cleared in HBM
         const V sl = ln + 64u * j;
-        const P in = W::ltu(sl, (uint32_t)p.Z);
+        const P in = W::ltu(sl, (uint32_t)SF_SHAPE(Z));
         const bool used = j < S.zwn;
         const V zpw = used ? zl_get(S, ZW_POS, j) : V(0u);
         W::gstore(z + ZW_POS * AZ, sl, zpw, in);
@@ -2129,16 +2138,16 @@ struct Core {
         zlive_n += (uint32_t)W::popc64(W::ballot((zpw & ZF_ALIVE) != 0u));
       }
     } else {
-      const P in = W::ltu(ln, (uint32_t)p.Z);
-      uint32_t *z = p.zom + (size_t)a * (size_t)p.Z;
+      const P in = W::ltu(ln, (uint32_t)SF_SHAPE(Z));
+      uint32_t *z = p.zom + (size_t)a * (size_t)SF_SHAPE(Z);
       W::gstore(z + ZW_POS * AZ, ln, S.zpos, in), W::gstore(z + ZW_HP * AZ, ln, S.zhp, in);
       W::gstore(z + ZW_MINDAMAGE * AZ, ln, S.zmd, in);
     }
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const V sl = ln + (uint32_t)(64 * j);
-      const P in = W::ltu(sl, (uint32_t)p.B);
-      uint32_t *b = p.bul + (size_t)a * (size_t)p.B;
+      const P in = W::ltu(sl, (uint32_t)SF_SHAPE(B));
+      uint32_t *b = p.bul + (size_t)a * (size_t)SF_SHAPE(B);
       W::gstore(b + BW_A * AB, sl, S.ba[j], in), W::gstore(b + BW_DAMAGE * AB, sl, S.bd[j], in);
       W::gstore(b + BW_B * AB, sl, S.bb[j], in), W::gstore(b + BW_C * AB, sl, S.bc[j], in);
     }
@@ -2171,15 +2180,15 @@ struct Core {
     W::setlane(sc, SC_WARM, S.warm);
     W::setlane(sc, SC_PD01, S.pd01), W::setlane(sc, SC_PD23, S.pd23), W::setlane(sc, SC_PD45, S.pd45);
     if constexpr (ZL) {
-      W::setlane(sc, SC_LOAD, zlive_n + (uint32_t)W::popc64(W::ballot(((S.hfl & HF_ALIVE) != 0u) & W::ltu(ln, (uint32_t)p.H))));
+      W::setlane(sc, SC_LOAD, zlive_n + (uint32_t)W::popc64(W::ballot(((S.hfl & HF_ALIVE) != 0u) & W::ltu(ln, (uint32_t)SF_SHAPE(H)))));
       W::setlane(sc, SC_ZWN, S.zwn);
       W::setlane(sc, SC_PWN, S.pwn);
     } else {
-      W::setlane(sc, SC_LOAD, (uint32_t)(W::popc64(W::ballot(((S.zpos & ZF_ALIVE) != 0u) & W::ltu(ln, (uint32_t)p.Z))) +
-                                         W::popc64(W::ballot(((S.hfl & HF_ALIVE) != 0u) & W::ltu(ln, (uint32_t)p.H)))));
+      W::setlane(sc, SC_LOAD, (uint32_t)(W::popc64(W::ballot(((S.zpos & ZF_ALIVE) != 0u) & W::ltu(ln, (uint32_t)SF_SHAPE(Z)))) +
+                                         W::popc64(W::ballot(((S.hfl & HF_ALIVE) != 0u) & W::ltu(ln, (uint32_t)SF_SHAPE(H))))));
     }
     W::gstore((uint32_t *)p.scal + (size_t)a * SC_WORDS, ln, sc, W::ltu(ln, (uint32_t)SC_WORDS));
-    if (!HBM_PLANE && S.dirty) W::copy_l2g(p.flags + (size_t)a * (size_t)p.cells_pad, lds, (uint32_t)p.cells_pad);
+    if (!HBM_PLANE && S.dirty) W::copy_l2g(p.flags + (size_t)a * (size_t)SF_SHAPE(cells_pad), lds, (uint32_t)SF_SHAPE(cells_pad));
   }
 
   // ------------------------------------------------------------------------------------------------
@@ -2197,19 +2206,19 @@ struct Core {
     S.ht = reinterpret_cast<const uint32_t *>(tab + LDS_EXP_BYTES);
     S.bm = nullptr;
     if (BITMAPS) {
-      S.bm = reinterpret_cast<uint32_t *>(lds + p.lds_tab + (HBM_PLANE ? 0 : p.cells_pad));
-      W::lds_zero(S.bm, (uint32_t)(BM_COUNT * p.bm_words));
+      S.bm = reinterpret_cast<uint32_t *>(lds + p.lds_tab + (HBM_PLANE ? 0 : SF_SHAPE(cells_pad)));
+      W::lds_zero(S.bm, (uint32_t)(BM_COUNT * SF_SHAPE(bm_words)));
     }
     S.zl = nullptr, S.zcap = 0u, S.zwn = 0u, S.zwhi = 0u;
     S.pl = nullptr, S.pwn = 0u, S.pwhi = 0u;
     if constexpr (ZL) {
-      S.zl = reinterpret_cast<uint32_t *>(lds + p.lds_tab + (HBM_PLANE ? 0 : p.cells_pad) + (BITMAPS ? BM_COUNT * 4 * p.bm_words : 0));
-      S.zcap = 64u * (uint32_t)zw_for(p.Z);
+      S.zl = reinterpret_cast<uint32_t *>(lds + p.lds_tab + (HBM_PLANE ? 0 : SF_SHAPE(cells_pad)) + (BITMAPS ? BM_COUNT * 4 * SF_SHAPE(bm_words) : 0));
+      S.zcap = 64u * (uint32_t)zw_for(SF_SHAPE(Z));
       S.pl = S.zl + ZW_WORDS * S.zcap;
     }
     S.la = V(0u);
     S.la2 = V(0u), S.la2_ok = 0u;
-    return HBM_PLANE ? p.flags + (size_t)a * (size_t)p.cells_pad : lds + p.lds_tab;
+    return HBM_PLANE ? p.flags + (size_t)a * (size_t)SF_SHAPE(cells_pad) : lds + p.lds_tab;
   }
 
   static SF_DEV void reset_body(uint8_t *lds, const Params &p, int a, const uint64_t *tb, const uint64_t *serial) {
@@ -2218,7 +2227,7 @@ struct Core {
     S.pd01 = S.pd23 = S.pd45 = 0u;
     lds = tables(S, lds, p, a);
     S.rl2 = V(RL_ZERO), S.rseed2 = V(0u), S.warm = 0u, S.wrate = 1u;
-    if constexpr (ZL) S.zwhi = (uint32_t)zw_for(p.Z), S.pwhi = (uint32_t)zw_for(p.P);  // store() writes the whole tables once: slots beyond zwn / pwn are zero in HBM from here on
+    if constexpr (ZL) S.zwhi = (uint32_t)zw_for(SF_SHAPE(Z)), S.pwhi = (uint32_t)zw_for(p.P);  // store() writes the whole tables once: slots beyond zwn / pwn are zero in HBM from here on
     reset_state(S, lds, p, tb[a], serial[a], false);
     ++S.frame;  // G:1441
     loop_top(S, lds, p, a);
@@ -2244,8 +2253,8 @@ struct Core {
     typename W::template G2L<4> q_pl;
     uint8_t *const tab0 = lds;
     const uint32_t ht_n = (uint32_t)p.ht_bytes < 2048u ? (uint32_t)p.ht_bytes : 2048u;
-    const uint32_t pl_n = HBM_PLANE ? 0u : ((uint32_t)p.cells_pad < 4096u ? (uint32_t)p.cells_pad : 4096u);
-    const uint8_t *const pl_g = p.flags + (size_t)a * (size_t)p.cells_pad;
+    const uint32_t pl_n = HBM_PLANE ? 0u : ((uint32_t)SF_SHAPE(cells_pad) < 4096u ? (uint32_t)SF_SHAPE(cells_pad) : 4096u);
+    const uint8_t *const pl_g = p.flags + (size_t)a * (size_t)SF_SHAPE(cells_pad);
     W::g2l_issue(q_exp, reinterpret_cast<const uint8_t *>(p.exptab), (uint32_t)LDS_EXP_BYTES);
     W::g2l_issue(q_ht, reinterpret_cast<const uint8_t *>(p.tab->hatab), ht_n);
     W::g2l_issue(q_pl, pl_g, pl_n);
@@ -2257,10 +2266,10 @@ struct Core {
       W::copy_g2l(tab0 + LDS_EXP_BYTES + ht_n, reinterpret_cast<const uint8_t *>(p.tab->hatab) + ht_n, (uint32_t)p.ht_bytes - ht_n);
     if (!HBM_PLANE) {
       W::g2l_store(q_pl, lds, pl_n);
-      if ((uint32_t)p.cells_pad > pl_n) W::copy_g2l(lds + pl_n, pl_g + pl_n, (uint32_t)p.cells_pad - pl_n);
+      if ((uint32_t)SF_SHAPE(cells_pad) > pl_n) W::copy_g2l(lds + pl_n, pl_g + pl_n, (uint32_t)SF_SHAPE(cells_pad) - pl_n);
     }
     draw_issue(S, p);  // the lookup of the next draw (S.la) is not part of the stored state; it reads the tables in LDS
-    const P ag = W::ltu(W::lane(), (uint32_t)p.n_agents);
+    const P ag = W::ltu(W::lane(), (uint32_t)SF_SHAPE(n_agents));
     // An episode shorter than its successor's warm-up stalls its own restart on the missing draws, and a launch is as
     // slow as its slowest arena: 17 % of configs[1]'s episodes are shorter than the 256 steps that 4 draws per step
     // would need, 0.7 % shorter than the 64 steps of 16 per step.  Measured over 4 / 8 / 16 / 32 / 64 draws per step:
@@ -2270,7 +2279,7 @@ struct Core {
     SF_STAMP_LOADED();
     SF_STAMP_BEGIN(S);
     for (int s = 0; s < k; ++s) {
-      const uint8_t *c = cmds + ((size_t)s * (size_t)p.A + (size_t)a) * (size_t)p.n_agents;
+      const uint8_t *c = cmds + ((size_t)s * (size_t)p.A + (size_t)a) * (size_t)SF_SHAPE(n_agents);
       S.hcmd = W::select(ag, W::gload_u8(c, W::lane(), ag), V((uint32_t)'+'));
       step<0, LOG>(S, lds, p, a);
     }
@@ -2291,13 +2300,14 @@ struct Core {
       S.hcmd = V((uint32_t)'+');  // (nothing reads a command before human_action)
       step<1>(S, lds, p, a);
     } else {
-      const P ag = W::ltu(W::lane(), (uint32_t)p.n_agents);
-      S.hcmd = W::select(ag, W::gload_u8(cmds + (size_t)a * (size_t)p.n_agents, W::lane(), ag), V((uint32_t)'+'));
+      const P ag = W::ltu(W::lane(), (uint32_t)SF_SHAPE(n_agents));
+      S.hcmd = W::select(ag, W::gload_u8(cmds + (size_t)a * (size_t)SF_SHAPE(n_agents), W::lane(), ag), V((uint32_t)'+'));
       step<2>(S, lds, p, a);
     }
     SF_STAMP_END(S, a);
     store(S, lds, p, a);
   }
 };
+#undef SF_SHAPE
 
 }  // namespace sf

@@ -187,6 +187,13 @@ struct has_ep_late : std::false_type {};
 template <class R>
 struct has_ep_late<R, decltype((void)std::declval<R &>().launch_ep_late(std::declval<const Params &>(), true))> : std::true_type {};
 
+// whether a runtime has the fixed-shape step kernels (k_step_fixed; sf_types.hpp FixedShapes): it then carries the index
+// Env::create picked in `fixed_shape`.  The HIP runtime has them; the emulator's runtime of tests/emu runs generic instances
+template <class R, class = void>
+struct has_fixed_shapes : std::false_type {};
+template <class R>
+struct has_fixed_shapes<R, decltype((void)std::declval<R &>().fixed_shape)> : std::true_type {};
+
 template <class RT>
 struct Env {
   sf_config cfg;
@@ -263,6 +270,13 @@ struct Env {
       if (r) rank_k_min = atoi(r);
       const char *ev = getenv("SF_RANK_EVERY");
       if (ev && atoi(ev) > 0) rank_every = atoi(ev);
+    }
+    // the step kernel of a listed configuration (sf_types.hpp FixedShapes), chosen here once: every fixed field of `p`
+    // equals the shape's.  SF_STEP_GENERIC=1 keeps the generic instance (A/B measurements, tests); while the episode log
+    // is on the runtime launches the generic LOG instance whatever was chosen here
+    if constexpr (has_fixed_shapes<RT>::value) {
+      const char *g = getenv("SF_STEP_GENERIC");
+      rt.fixed_shape = (g && g[0] == '1' && !g[1]) ? -1 : fixed_shape_of(p, FixedShapes{});
     }
     // tables: one shared player record (block 0) + npc (block 1), or one record per commanded human (blocks 0..15,
     // the account blobs of a lock-step match, gameplay.hpp:120-151) + npc (block 16)

@@ -173,11 +173,11 @@ constexpr int LOGT_ENTRIES = LOGT_OFF + 65537;
 
 // Per-arena scratch bitmaps in LDS, one bit per cell (sf_core.hpp "cell bitmaps"): only with the flag plane in LDS
 constexpr int BM_COUNT = 3;
-inline int bm_words_for(int cells);
+constexpr int bm_words_for(int cells);
 // bitmaps are used when the three of them take at most 6 KiB of LDS per arena (maps up to 128 x 128 cells): with the
 // flag plane in LDS (<= 12 KiB) that always holds, with the plane in HBM it admits 128 x 128 but not 256 x 256
 inline bool use_bitmaps(int cells_pad) { return BM_COUNT * 4 * bm_words_for(cells_pad) <= 6 * 1024; }
-inline int bm_words_for(int cells) { return ((cells + 31) / 32 + 3) & ~3; }  // words per bitmap, 16-byte multiple
+constexpr int bm_words_for(int cells) { return ((cells + 31) / 32 + 3) & ~3; }  // words per bitmap, 16-byte multiple
 
 inline int nb_for(int B) { return (B + 63) / 64; }
 // Zombie or exit pools of more than 64 slots (the reference's hold 9000, gameplay.hpp:37,51-53) live in LDS instead of
@@ -201,6 +201,68 @@ inline size_t lds_bytes_for(int cells_pad, int lds_tab, int Z, int P) {
 // flag planes above this size stay in HBM (Core<.., HBM_PLANE>): staging them would leave < 12 wavefronts per CU
 constexpr int LDS_PLANE_MAX = 12 * 1024;
 inline bool hbm_plane(int cells_pad) { return cells_pad > LDS_PLANE_MAX; }
+
+// ---- shape policy (sf_core.hpp Core<.., SH>) -----------------------------------------------------------------------
+// The configuration fields below are set by sf_create and never change over an environment's life.  The device core reads
+// them through a shape type (sf_core.hpp SF_SHAPE): RuntimeShape hands out the Params field (every generic kernel instance),
+// FixedShape<..> hands out compile-time constants (k_step_fixed, sf_api.hip), which lets the compiler fold the fields and every
+// loop-invariant condition derived from them instead of keeping them in (spilled) scalar registers over the step loop.
+// Pointers, A, P, reseed, timer_lim, perm and everything else in Params are run-time values under both.
+#define SF_SHAPE_FIELDS(X) X(F) X(N) X(M) X(cells) X(cells_pad) X(bm_words) X(H) X(Z) X(B) X(mode) X(level) X(n_agents) X(auto_reset) X(ind)
+struct RuntimeShape {
+  static constexpr bool FIXED = false;
+#define SF_SHAPE_ACCESSOR(f) \
+  static SF_HD int32_t f(const Params &p) { return p.f; }
+  SF_SHAPE_FIELDS(SF_SHAPE_ACCESSOR)
+#undef SF_SHAPE_ACCESSOR
+};
+template <int F_, int N_, int M_, int H_, int Z_, int B_, int MODE_, int LEVEL_, int N_AGENTS_, int AUTO_RESET_, int IND_>
+struct FixedShape {
+  static constexpr bool FIXED = true;
+  struct Values {  // the constants under the names of the Params fields they stand for
+    static constexpr int32_t F = F_, N = N_, M = M_, cells = F_ * N_ * M_, cells_pad = (cells + 15) & ~15,
+                             bm_words = bm_words_for(cells_pad), H = H_, Z = Z_, B = B_, mode = MODE_, level = LEVEL_,
+                             n_agents = N_AGENTS_, auto_reset = AUTO_RESET_, ind = IND_;
+  };
+  // built for the instance every throughput configuration runs: flag plane and bitmaps in LDS, register slot pools
+  static_assert(Values::cells_pad <= LDS_PLANE_MAX && Z_ <= 64 && H_ <= 64 && B_ <= 256, "a fixed shape is an LDS-plane, register-pool shape");
+  static constexpr int NB = (B_ + 63) / 64;
+#define SF_SHAPE_ACCESSOR(f) \
+  static SF_HD constexpr int32_t f(const Params &) { return Values::f; }
+  SF_SHAPE_FIELDS(SF_SHAPE_ACCESSOR)
+#undef SF_SHAPE_ACCESSOR
+  // whether an environment of configuration `p` may run this shape's instance: every fixed field equal, and the generic
+  // instance it would run otherwise is <NB, LDS plane, bitmaps, register pools> too (P is not fixed: more than 64 exits
+  // move the pools to LDS)
+  static bool matches(const Params &p) {
+#define SF_SHAPE_EQUAL(f) &&p.f == Values::f
+    return !large_pools(p.Z, p.P) SF_SHAPE_FIELDS(SF_SHAPE_EQUAL);
+#undef SF_SHAPE_EQUAL
+  }
+};
+template <class... S>
+struct ShapeList {};
+// The fixed shapes built, one k_step_fixed instance each (about 10 s of build time; 42 980 B and 26 772 B of code for the
+// two below): one line per shape.
+//             F  N   M   H  Z   B   mode                level  n_agents  auto_reset  ind
+using FixedShapes = ShapeList<
+    FixedShape<1, 64, 64, 8, 24, 64, 1 /* SF_MODE_TIMER */, 1, 1, 1, 0>,  // BASELINE configs[2]: 64 x 64, 32 entities, Timer
+    FixedShape<1, 64, 64, 1, 16, 32, 0 /* SF_MODE_SOLO */, 1, 1, 1, 0>    // BASELINE configs[1]: 64 x 64, 1 player + 16 zombies, Solo
+    >;
+// index in the list of the first shape configuration `p` matches, -1 if none (Env::create, once per environment)
+inline int fixed_shape_of(const Params &, ShapeList<>, int = 0) { return -1; }
+template <class S0, class... S>
+inline int fixed_shape_of(const Params &p, ShapeList<S0, S...>, int first = 0) {
+  return S0::matches(p) ? first : fixed_shape_of(p, ShapeList<S...>{}, first + 1);
+}
+// f(S{}) for shape number `index` of the list (a value fixed_shape_of returned); returns f's int, `none` where the list
+// has no such shape
+template <class F>
+inline int with_fixed_shape(int, ShapeList<>, int none, F &&) { return none; }
+template <class F, class S0, class... S>
+inline int with_fixed_shape(int index, ShapeList<S0, S...>, int none, F &&f) {
+  return index == 0 ? f(S0{}) : with_fixed_shape(index - 1, ShapeList<S...>{}, none, f);
+}
 
 // The instances of the per-arena kernels (k_reset, k_step, k_step_half; Core<W, NB, HP, BM, ZL>) and the one a configuration
 // runs.  Built: NB 1..4 x {(HP 0, BM 1), (HP 1, BM 1), (HP 1, BM 0)}, and the same three with ZL (large pools) for NB 4 —

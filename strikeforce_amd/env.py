@@ -72,6 +72,9 @@ def load_library():
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
+        if hasattr(L, "sf_step_kernel"):  # (an older build loaded through SF_LIBRARY_PATH lacks it)
+            L.sf_step_kernel.argtypes = [vp, C.POINTER(C.c_int32)]
+            L.sf_step_kernel.restype = C.c_int
         L.sf_comm_unique_id.argtypes = [C.c_char_p]
         L.sf_comm_init.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32]
         L.sf_results_allgather.argtypes = [vp, vp]
@@ -98,7 +101,7 @@ REPLAY_EXPORTS = ("sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_re
 # every symbol include/strikeforce.h declares
 EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step", "sf_step_device", "sf_observe",
            "sf_observe_device", "sf_observe_device_delta", "sf_observe_sparse_device", "sf_observe_overflow_device", "sf_results", "sf_results_device", "sf_done", "sf_done_device", "sf_done_view_device", "sf_state_digest", "sf_dump_arena",
-           "sf_set_stream", "sf_synchronize", "sf_kernel_time", "sf_last_error", "sf_abi_version",
+           "sf_set_stream", "sf_synchronize", "sf_kernel_time", "sf_step_kernel", "sf_last_error", "sf_abi_version",
            "sf_comm_unique_id", "sf_comm_init", "sf_results_allgather", "sf_comm_wait", "sf_comm_ranks",
            "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
@@ -401,6 +404,12 @@ class ArenaBatch:
         hdr, hs, zs, bs, ps, flags, dmg, pidx = self.dump_raw(arena)
         return types.SimpleNamespace(hdr=hdr, humans=hs, zombies=zs, bullets=bs, portals=ps, flags=flags, dmg=dmg,
                                      pidx=pidx)
+
+    def step_kernel(self):
+        """Index of the fixed-shape kernel the last step launch ran (csrc/sf_types.hpp FixedShapes), -1: a generic instance."""
+        i = C.c_int32(-2)
+        self._ck(self.L.sf_step_kernel(self.h, C.byref(i)), "sf_step_kernel")
+        return i.value
 
     def kernel_time(self, enable=True):
         """(ms, launches) of the step kernels since the last call, from HIP events on the launch stream."""

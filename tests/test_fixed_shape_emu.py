@@ -1,0 +1,234 @@
+"""The fixed-shape step kernel's body without a GPU: Core<WaveEmu, 1, false, true, false, FixedShape<C3>> (sf_core.hpp
+with BASELINE configs[2]'s configuration fields as compile-time constants, sf_types.hpp FixedShapes) on the wave emulator,
+selected by the product's own host code (sf_host.hpp Env::create), against the oracle and against the generic emulator
+instance, digest by digest.  The shim is tests/fixed_shape_emu/sf_emu_fixed.cpp: tests/emu's build plus a runtime that
+carries the fixed-shape launch path.
+
+The world is C3's shape with a sturdy player who fires now and then, armed NPC humans, and a Timer game of 1 300 frames
+(timer_lim is not a fixed field), 720 steps.  A step is two frames and a zombie is spawned at most every 40 frames, so the
+cap of 24 zombies cannot be reached before step 480, whatever the seed (the oracle's own runs reach it between steps 480
+and 620); 300 steps would end with 15 zombies at most.  The game ends after 650 steps and restarts inside the run, so
+reset_state runs under the fixed shape with every pool populated before it."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import emu_lib
+from oracle_lib import Oracle, ROOT
+from strikeforce_amd import abi, config
+
+ARENAS, STEPS, TIMER_FRAMES = 4, 720, 1300
+C3_SHAPE, C2_SHAPE = 0, 1  # index of BASELINE configs[2] / configs[1] in sf_types.hpp FixedShapes
+
+
+@pytest.fixture(scope="module")
+def shim():
+    d = os.path.join(ROOT, "tests", "fixed_shape_emu")
+    # make is a no-op when the file __graft_entry__.build() made is up to date with its sources
+    subprocess.check_call(["make", "-s", "-C", d, "libsf_emu_fixed.so"])
+    L = C.CDLL(os.path.join(d, "libsf_emu_fixed.so"))
+    L.sfx_create.argtypes = [C.POINTER(abi.Config)]
+    L.sfx_create.restype = C.c_void_p
+    abi.bind(L, "sfx_")
+    L.sfx_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+    L.sfx_last_error.restype = C.c_char_p
+    L.sfx_step_kernel.argtypes = [C.c_void_p]
+    return L
+
+
+class _AsEmu:
+    """The shim's sfx_ entry points under the sfe_ names emu_lib.Emu calls."""
+
+    def __init__(self, L):
+        self._L = L
+
+    def __getattr__(self, name):
+        return getattr(self._L, "sfx_" + name[4:] if name.startswith("sfe_") else name)
+
+
+class EmuFixed(emu_lib.Emu):
+    """emu_lib.Emu's surface over the shim's library, plus which step instance the last launch ran."""
+
+    def __init__(self, workload, L):
+        self.w, self.cfg, self.L = workload, workload.cfg, _AsEmu(L)
+        self.h = L.sfx_create(C.byref(self.cfg))
+        assert self.h, L.sfx_last_error().decode()
+
+    def step_kernel(self):
+        return self.L.sfx_step_kernel(self.h)
+
+
+def world(arenas=ARENAS):
+    w = config.baseline_workload("C3", arenas=arenas)
+    w.cfg.timer_frames_per_level = TIMER_FRAMES
+    t = list(config.HUMAN_ENEMY_TOKENS)
+    t[0] = 1_000_000  # hp: the player outlasts the herd, the game ends by its timer
+    w.cfg.player = abi.Profile.from_tokens(t)
+    return w
+
+
+def commands(arenas=ARENAS, steps=STEPS, seed=3):
+    """[steps][arenas][1]: the player stands ('+'), selects weapon 4 ('m') every 64 steps, fires ('x') every 16 and turns
+    ('q') on ~3 % of the steps: bullets fly, and the zombies are left to fill their pool."""
+    r = np.random.RandomState(seed)
+    out = np.full((steps, arenas, 1), ord("+"), dtype=np.uint8)
+    s = np.arange(steps)
+    out[s % 16 == 1] = ord("x")
+    out[s % 64 == 0] = ord("m")
+    out[r.random_sample((steps, arenas, 1)) < 0.03] = ord("q")
+    return out
+
+
+@pytest.fixture(scope="module")
+def oracle_run():
+    """The oracle's digests after every step, and what the run reached; computed once."""
+    w = world()
+    o = Oracle(w)
+    o.reset(*w.seeds())
+    cmds = commands()
+    digests = np.zeros((STEPS, ARENAS), dtype=np.uint64)
+    zombies, bullets, npcs = np.zeros(ARENAS, int), np.zeros(ARENAS, int), np.zeros(ARENAS, int)
+    for s in range(STEPS):
+        o.step(cmds[s])
+        digests[s] = o.digest()
+        if s % 5 == 4:
+            for a in range(ARENAS):
+                d = o.dump(a)
+                zombies[a] = max(zombies[a], sum(1 for z in d.zombies if z.alive))
+                bullets[a] = max(bullets[a], sum(1 for b in d.bullets if b.alive))
+                npcs[a] = max(npcs[a], sum(1 for h in d.humans[1:] if h.alive))
+    episodes = np.array([o.dump(a).hdr.episodes for a in range(ARENAS)])
+    frames = np.array([o.dump(a).hdr.frame for a in range(ARENAS)])
+    out = dict(digests=digests, zombies=zombies, bullets=bullets, npcs=npcs, episodes=episodes, frames=frames,
+               results=o.results(), done=o.done())
+    o.close()
+    return out
+
+
+def test_the_oracle_run_fills_the_pools_and_restarts(oracle_run):
+    r = oracle_run
+    print("most live zombies %s, bullets %s, NPC humans %s; episodes ended %s, frame at the end %s"
+          % (r["zombies"], r["bullets"], r["npcs"], r["episodes"], r["frames"]))
+    assert r["zombies"].max() == 24, "no arena's zombie pool reached its cap"
+    assert (r["bullets"] > 0).all() and (r["npcs"] > 0).all()
+    assert r["npcs"].max() == 7  # cap_humans 8: the player and seven NPC humans
+    assert (r["episodes"] >= 1).any(), "no game ended inside the run"
+    # ... and went on: the arena that ended a game is in the next one (a Timer game of 1 300 frames, 720 steps = 1 440)
+    assert (r["frames"][r["episodes"] >= 1] < TIMER_FRAMES).all()
+
+
+def test_fixed_shape_core_equals_oracle_and_generic_core(shim, oracle_run, monkeypatch):
+    w = world()
+    monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
+    f = EmuFixed(w, shim)
+    monkeypatch.setenv("SF_STEP_GENERIC", "1")
+    g = EmuFixed(world(), shim)
+    monkeypatch.delenv("SF_STEP_GENERIC")
+    tb, sr = w.seeds()
+    f.reset(tb, sr), g.reset(tb, sr)
+    cmds = commands()
+    for s in range(STEPS):
+        f.step(cmds[s]), g.step(cmds[s])
+        assert f.step_kernel() == C3_SHAPE and g.step_kernel() == -1, "step %d: instance" % s
+        df, dg = f.digest(), g.digest()
+        assert (df == oracle_run["digests"][s]).all(), "step %d: fixed-shape core differs from the oracle" % s
+        assert (dg == df).all(), "step %d: fixed-shape core differs from the generic core" % s
+    assert (f.results() == oracle_run["results"]).all() and (f.done() == oracle_run["done"]).all()
+    assert (g.results() == oracle_run["results"]).all()
+    f.close(), g.close()
+
+
+def test_long_launches_under_the_fixed_shape(shim, oracle_run, monkeypatch):
+    """The step loop inside one launch (k = 7 and 100), as sf_step_device runs it."""
+    monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
+    w = world()
+    f = EmuFixed(w, shim)
+    f.reset(*w.seeds())
+    cmds = commands()
+    s = 0
+    for k in (7, 100, 100, 100, 100, 100, 100, 100, 13):
+        f.step_many(cmds[s:s + k])
+        s += k
+        assert f.step_kernel() == C3_SHAPE
+        assert (f.digest() == oracle_run["digests"][s - 1]).all(), "after %d steps" % s
+    assert s == STEPS
+    f.close()
+
+
+@pytest.mark.parametrize("change", ["H 9", "Z 25", "64 x 63", "2 x 32 x 64", "two floors", "Solo", "Squad", "two agents", "level 2", "no auto_reset", "B 65", "P 65"])
+def test_any_other_configuration_selects_the_generic_instance(shim, change, monkeypatch):
+    """One fixed field off C3's shape (and P past the register pools): the host must not pick the fixed instance."""
+    monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
+    w = other_world(change, 2)
+    e = EmuFixed(w, shim)
+    e.reset(*w.seeds())
+    cmds, _ = config.bench_commands(2, w.cfg.n_agents, 3)
+    for s in range(3):
+        e.step(cmds[s])
+        assert e.step_kernel() == -1
+    e.close()
+
+
+def test_c2_shape_core_equals_oracle_and_generic_core(shim, monkeypatch):
+    """The second shape of the table, BASELINE configs[1] (Solo, 1 player + 16 zombies) under the random-action agent, 400
+    steps: the oracle's own run fills the zombie pool and ends a game in one of the four arenas."""
+    A, steps = 4, 400
+    w = config.baseline_workload("C2", arenas=A)
+    monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
+    f = EmuFixed(w, shim)
+    monkeypatch.setenv("SF_STEP_GENERIC", "1")
+    g = EmuFixed(config.baseline_workload("C2", arenas=A), shim)
+    monkeypatch.delenv("SF_STEP_GENERIC")
+    o = Oracle(config.baseline_workload("C2", arenas=A))
+    tb, sr = w.seeds()
+    f.reset(tb, sr), g.reset(tb, sr), o.reset(tb, sr)
+    cmds, _ = config.bench_commands(A, 1, steps)
+    zombies = 0
+    for s in range(steps):
+        f.step(cmds[s]), g.step(cmds[s]), o.step(cmds[s])
+        assert f.step_kernel() == C2_SHAPE and g.step_kernel() == -1
+        want = o.digest()
+        assert (f.digest() == want).all() and (g.digest() == want).all(), "step %d" % s
+        if s % 10 == 9:
+            zombies = max(zombies, max(sum(1 for z in o.dump(a).zombies if z.alive) for a in range(A)))
+    assert zombies == 16 and sum(o.dump(a).hdr.episodes for a in range(A)) >= 1
+    assert (f.results() == o.results()).all()
+    f.close(), g.close(), o.close()
+
+
+def other_world(change, arenas):
+    """C3 with one fixed field changed, where sf_create admits that."""
+    kw = dict(H=8, Z=24, B=64, P=8, mode=abi.MODE_TIMER)
+    floors, rows, cols = 1, 64, 64
+    if change == "H 9":
+        kw["H"] = 9
+    elif change == "Z 25":
+        kw["Z"] = 25
+    elif change == "B 65":
+        kw["B"] = 65
+    elif change == "P 65":
+        kw["P"] = 65
+    elif change == "64 x 63":
+        cols = 63
+    elif change == "2 x 32 x 64":  # F and N off the shape, every derived size (cells, cells_pad, bm_words) equal to C3's
+        floors, rows = 2, 32
+    elif change == "two floors":  # F alone (the derived sizes follow)
+        floors = 2
+    elif change == "Solo":
+        kw["mode"] = abi.MODE_SOLO
+    elif change == "Squad":  # (sf_create wants ten human slots for a Squad game: H is off the shape too)
+        kw["mode"], kw["H"] = abi.MODE_SQUAD, 10
+    elif change == "two agents":  # (and more than one commanded human only outside Solo and Timer)
+        kw["mode"], kw["H"], kw["n_agents"] = abi.MODE_SQUAD, 10, 2
+    elif change == "level 2":
+        kw["level"] = 2
+    elif change == "no auto_reset":
+        kw["auto_reset"] = 0
+    else:
+        raise ValueError(change)
+    cfg = config.make_config(arenas, rows, cols, floors=floors, **kw)
+    m, p = config.synthetic_map(rows, cols, floors=floors)
+    return config.Workload("c3-" + change, cfg, m, p)
