@@ -13,17 +13,20 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libstrikeforce_amd.so")
 SOURCES = ["sf_api.hip", "sf_policy.hip"]
-DEPS = ["sf_api.hip", "sf_policy.hip", "sf_core.hpp", "sf_obs.hpp", "sf_obs_kernels.hpp", "sf_host.hpp", "sf_types.hpp",
-        "wave_gfx950.hpp",
-        os.path.join("..", "..", "include", "strikeforce.h"),
-        os.path.join("..", "..", "include", "strikeforce_policy.h")]
+
+
+def deps():
+    """Every source and header under csrc/ and the two public headers: a new file there is a dependency at once."""
+    inc = os.path.join(HERE, "..", "include")
+    return ([os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith((".hip", ".hpp"))]
+            + [os.path.join(inc, "strikeforce.h"), os.path.join(inc, "strikeforce_policy.h")])
 
 
 def stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    return any(os.path.getmtime(os.path.join(CSRC, d)) > t for d in DEPS)
+    return any(os.path.getmtime(d) > t for d in deps())
 
 
 def build(force=False, verbose=True):

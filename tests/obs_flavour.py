@@ -31,7 +31,7 @@ def stale():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f != "sf_policy.hip"]
+    deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if not f.startswith("sf_policy")]
     deps += [os.path.join(ROOT, "include", "strikeforce.h"), os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
