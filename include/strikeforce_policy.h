@@ -238,6 +238,113 @@ int sf_policy_features(sf_policy *p, const float *d_obs, int32_t agents, float *
 
 int sf_policy_abi_version(void);
 
+/* ---- the rollout buffer: bot-1's T-step record, returns and advantages (StrikeForce-client/bots/bot-1/Agent.hpp) --------
+ * One reference `Agent` keeps five vectors per game — states, log_probs, values, rewards, actions (Agent.hpp:200-204, 227,
+ * 233-234, 301-302) — fills them for T = 1024 ticks, then runs computeReturns() (:333-339) and train_log() (:341-351) over
+ * them; its PPO epochs and RewardNet::train_epoch forward states[i] again from a fresh memory (:389-396,
+ * RewardNet.hpp:265-274).  An sf_rollout does that bookkeeping and that gradient-free arithmetic for every agent of a
+ * batch on the device, behind sf_policy_predict_sparse and sf_reward_sparse.  The learners themselves — gradients, AdamW,
+ * backups — stay out of scope.
+ *
+ * Storage is the caller's, as every other buffer of this library is: device pointers, slot-major, for the `agents` and T
+ * given to sf_rollout_create.  The library owns the per-agent cursor fill[agents] and three counters.
+ *   keys, vals   [T][agents][list_cap]   states.push_back(state) (:201) as the observation list; 16-byte aligned
+ *   counts       [T][agents]             the list's count as it came
+ *   pov          [T][agents][160]        the five centre cells; 16-byte aligned
+ *   action       [T][agents] int32       actions.push_back(action) (:234)
+ *   logp         [T][agents][9]          log_probs.push_back(torch::log(output[0])) (:204): the f32 log, rounded once
+ *   value        [T][agents]             values.push_back(output[1]) (:203)
+ *   reward       [T][agents]             rewards.push_back(get_reward(...)) (:227)
+ *   disc         [T][agents]             optional (NULL: not kept): D beside its log
+ *   imitate      [T][agents] u8          optional (NULL: not kept): get_reward's `imitate` argument
+ * keys == NULL: states are not kept (vals, counts and pov are not looked at).  Every other pointer is required. */
+typedef struct sf_rollout sf_rollout;
+typedef struct sf_rollout_buffers {
+  uint32_t *keys;
+  float *vals;
+  uint32_t *counts;
+  float *pov;
+  int32_t *action;
+  float *logp, *value, *reward;
+  float *disc;
+  uint8_t *imitate;
+} sf_rollout_buffers;
+
+/* SF_ERR_ARG: T odd or below 2 (the reference's sum_rewards[i / (T / 2)], :344, indexes out of bounds for an odd T);
+ * list_cap % 4 != 0 or outside [4, SF_POLICY_LIST_MAX] (only looked at when states are kept); agents outside
+ * [1, 1048576]; a required pointer NULL or keys / vals / pov not 16-byte aligned.  Every cursor starts at 0. */
+int sf_rollout_create(const sf_rollout_buffers *b, int32_t agents, int32_t T, int32_t list_cap, int32_t device, sf_rollout **out);
+void sf_rollout_destroy(sf_rollout *r);
+int sf_rollout_set_stream(sf_rollout *r, void *hip_stream);
+int sf_rollout_synchronize(sf_rollout *r);
+
+/* One tick of agents [0, agents): Agent::predict()'s and Agent::update()'s push_backs (:201-204, 227, 234).  One launch,
+ * no synchronisation; issue it behind sf_reward_sparse and in front of sf_step_device on the same stream, so that it
+ * reads the restart flags those two calls read.
+ *   d_keys .. cap        this tick's observation lists, as in sf_policy_predict_io; not looked at when states are not kept
+ *   d_probs [agents][9], d_value [agents], d_action [agents]   sf_policy_predict_sparse's outputs
+ *   d_reward [agents]    sf_reward_sparse's output; d_disc [agents], d_imitate [agents]: required exactly when the
+ *                        buffer of that name is kept, not looked at otherwise
+ *   d_reset_mask / d_reset_words, reset_stride, reset_group    as in sf_policy_predict_io
+ * Per agent, in this order:
+ *   1. fill == T: the agent is ready.  Nothing is written, its restart flag is not looked at, the tick is counted in
+ *      `dropped` — the `if (is_training ...) return;` of :219.
+ *   2. its restart flag is set: fill = 0 (a new Agent per game; ~Agent trains nothing from a partial buffer).
+ *   3. the tick is appended at slot `fill`: min(count, list_cap) list entries (never more than cap) and the 160 pov floats;
+ *      the count as it came — above list_cap, or the 0xffffffff marker, it is stored unchanged and counted in
+ *      `missing_states`, so that sf_policy_forward_sparse on the stored row sees "did not fit" as the live call did;
+ *      action, value, reward, disc and imitate bit for bit; logp[j] = the f32 log of d_probs[j]; then fill += 1.
+ *      Entries of a stored row behind the count are not written. */
+typedef struct sf_rollout_step {
+  const uint32_t *d_keys;
+  const float *d_vals;
+  const uint32_t *d_counts;
+  const float *d_pov;
+  int32_t cap;
+  int32_t agents;
+  const float *d_probs, *d_value;
+  const int32_t *d_action;
+  const float *d_reward, *d_disc;
+  const uint8_t *d_imitate;
+  const uint8_t *d_reset_mask;
+  const int32_t *d_reset_words;
+  int32_t reset_stride, reset_group;
+} sf_rollout_step;
+int sf_rollout_record(sf_rollout *r, const sf_rollout_step *io);
+
+/* *d_fill: the cursors (device, int32 per agent, the library's; valid until sf_rollout_destroy).  d_mask[a] (device, one
+ * byte per agent) = fill[a] == T, the mask sf_policy_reset_memory takes (model->reset_memory(), :432).  sf_rollout_status
+ * synchronises: *ready = how many agents are ready now; *dropped and *missing_states count since sf_rollout_create.
+ * Any of its outputs may be NULL. */
+int sf_rollout_fill_device(sf_rollout *r, const int32_t **d_fill);
+int sf_rollout_ready_device(sf_rollout *r, uint8_t *d_mask);
+int sf_rollout_status(sf_rollout *r, int32_t *ready, int64_t *dropped, int64_t *missing_states);
+
+/* For the READY agents only (rows of the others are not touched), all [T][agents] device arrays, each may be NULL:
+ *   d_returns[T-1] = (1 - gamma) * reward[T-1];  d_returns[i] = gamma * d_returns[i+1] + (1 - gamma) * reward[i]   (:333-339)
+ *   d_logv = the f32 log of value (:401, :407);  d_adv = d_returns - d_logv   (:407)
+ *   d_stats [agents][4] (16-byte aligned) = r_avg0, r_avg1 — the sums of reward over each half of the buffer, DIVIDED BY T
+ *   as :347-348 divide them — and n_avg0, n_avg1, the share of action 0 in each half (:349-350)
+ * f32 in the reference's operation order: (1 - gamma) is an f32 subtraction, every product is rounded before the add (no
+ * fused multiply-add), the sums are sequential in slot order; infinities and NaNs fall out as IEEE gives them (D == 0 is a
+ * reward of -inf).  train_log's mean of exp(log_probs) is a log line and is left to the caller. */
+int sf_rollout_returns(sf_rollout *r, float gamma, float *d_returns, float *d_logv, float *d_adv, float *d_stats);
+
+/* clear() of the five vectors (:430-431): fill = 0 for every ready agent (d_mask NULL), or for the agents whose byte in
+ * d_mask (device, one per agent) is non-zero, ready or not. */
+int sf_rollout_release(sf_rollout *r, const uint8_t *d_mask);
+
+/* The four device pointers of slot t, with *cap = list_cap: states[t] of every agent, as sf_policy_forward_sparse and
+ * sf_reward_sparse take it.  SF_ERR_STATE when states are not kept; SF_ERR_ARG for t outside [0, T). */
+int sf_rollout_state(sf_rollout *r, int32_t t, const uint32_t **d_keys, const float **d_vals, const uint32_t **d_counts,
+                     const float **d_pov, int32_t *cap);
+
+/* AgentModel::update_actions(one_hot(d_action[a])) (Agent.hpp:396, RewardNet.hpp:271-272) for agents [0, agents) of a
+ * policy or a reward model; an index outside [0, 9) means 0, as in sf_reward_forward.  With it the stored rollout can be
+ * replayed: a fresh agent always starts at slot 0, so sf_policy_reset_memory followed by rows 0..T-1 — forward on
+ * the state of slot t, then this call on action[t] — reproduces every ready agent's sequence. */
+int sf_policy_update_actions(sf_policy *p, const int32_t *d_action, int32_t agents);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,6 +39,7 @@
 #include "sf_policy_gemm.hpp"
 #include "sf_policy_stage.hpp"
 #include "sf_policy_tail.hpp"
+#include "sf_rollout.hpp"
 
 namespace sfp {
 
@@ -782,6 +783,174 @@ int sf_policy_kernel_time(sf_policy *pp, int32_t enable, float *ms, double *flop
   if (ms) *ms = m[0] + m[1];
   if (flop) *flop = f[0] + f[1];
   if (launches) *launches = n[0] + n[1];
+  return SF_OK;
+}
+
+}  // extern "C"
+
+// ---- the rollout buffer (sf_rollout_*): the caller's storage, the library's cursors and counters -------------------------
+namespace sfp {
+struct Rollout {
+  int device = 0, agents = 0;
+  hipStream_t stream = nullptr;
+  RolloutDst d{};
+  ~Rollout() {
+    if (d.fill) (void)hipFree(d.fill);
+    if (d.counters) (void)hipFree(d.counters);
+  }
+};
+static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+static dim3 per_lane(int n) { return dim3((unsigned)((n + 255) / 256)); }
+}  // namespace sfp
+using sfp::Rollout;
+
+extern "C" {
+
+int sf_rollout_create(const sf_rollout_buffers *b, int32_t agents, int32_t T, int32_t list_cap, int32_t device, sf_rollout **out) {
+  if (!b || !out) return sfp::fail(SF_ERR_ARG, "null argument");
+  if (agents < 1 || agents > (1 << 20)) return sfp::fail(SF_ERR_ARG, "agents must be 1..1048576");
+  if (T < 2 || T % 2) return sfp::fail(SF_ERR_ARG, "T must be even and at least 2");
+  if (b->keys && (list_cap % 4 || list_cap < 4 || list_cap > SF_POLICY_LIST_MAX))
+    return sfp::fail(SF_ERR_ARG, "list_cap must be a multiple of 4 in [4, SF_POLICY_LIST_MAX]");
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return sfp::fail(SF_ERR_DEVICE, "no HIP device: the rollout buffer has no CPU path");
+  if (device < 0 || device >= n) return sfp::fail(SF_ERR_DEVICE, "device ordinal out of range");
+  if (!b->action || !b->logp || !b->value || !b->reward || (b->keys && (!b->vals || !b->counts || !b->pov)))
+    return sfp::fail(SF_ERR_ARG, "sf_rollout_buffers has a null pointer");
+  if (b->keys && (!sfp::aligned16(b->keys) || !sfp::aligned16(b->vals) || !sfp::aligned16(b->pov)))
+    return sfp::fail(SF_ERR_ARG, "keys, vals and pov must be 16-byte aligned");
+  SFP_HIP(hipSetDevice(device));
+  std::unique_ptr<Rollout> r(new Rollout());
+  r->device = device, r->agents = agents;
+  sfp::RolloutDst &d = r->d;
+  d.keys = b->keys, d.vals = b->vals, d.counts = b->counts, d.pov = b->pov, d.action = b->action, d.logp = b->logp;
+  d.value = b->value, d.reward = b->reward, d.disc = b->disc, d.imitate = b->imitate;
+  d.stride = agents, d.T = T, d.list_cap = b->keys ? list_cap : 0;
+  if (hipMalloc(reinterpret_cast<void **>(&d.fill), (size_t)agents * sizeof(int32_t)) != hipSuccess ||
+      hipMalloc(reinterpret_cast<void **>(&d.counters), 3 * sizeof(unsigned long long)) != hipSuccess)
+    return sfp::fail(SF_ERR_MEMORY, "hipMalloc failed (rollout)");
+  SFP_HIP(hipMemset(d.fill, 0, (size_t)agents * sizeof(int32_t)));
+  SFP_HIP(hipMemset(d.counters, 0, 3 * sizeof(unsigned long long)));
+  *out = reinterpret_cast<sf_rollout *>(r.release());
+  return SF_OK;
+}
+
+void sf_rollout_destroy(sf_rollout *r) { delete reinterpret_cast<Rollout *>(r); }
+
+int sf_rollout_set_stream(sf_rollout *rr, void *hip_stream) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r) return sfp::fail(SF_ERR_ARG, "null rollout");
+  r->stream = reinterpret_cast<hipStream_t>(hip_stream);
+  return SF_OK;
+}
+
+int sf_rollout_synchronize(sf_rollout *rr) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r) return sfp::fail(SF_ERR_ARG, "null rollout");
+  SFP_HIP(hipSetDevice(r->device));
+  SFP_HIP(hipStreamSynchronize(r->stream));
+  return SF_OK;
+}
+
+int sf_rollout_record(sf_rollout *rr, const sf_rollout_step *io) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r || !io) return sfp::fail(SF_ERR_ARG, "null rollout or io");
+  if (io->agents < 1 || io->agents > r->agents) return sfp::fail(SF_ERR_ARG, "agents out of range for this rollout");
+  const bool keep = r->d.keys != nullptr;
+  if (keep) SFP_RC(sfp::check_lists(io->d_keys, io->d_vals, io->d_counts, io->d_pov, io->cap));
+  if (!io->d_probs || !io->d_value || !io->d_action || !io->d_reward || (r->d.disc && !io->d_disc) || (r->d.imitate && !io->d_imitate))
+    return sfp::fail(SF_ERR_ARG, "null buffer");
+  SFP_RC(sfp::check_resets(io->d_reset_words, io->reset_stride, io->reset_group));
+  sfp::RolloutSrc s{};
+  if (keep) {
+    s.keys = io->d_keys, s.vals = io->d_vals, s.counts = io->d_counts, s.pov = io->d_pov, s.cap = io->cap;
+    s.vec = io->cap % 4 == 0 && sfp::aligned16(io->d_keys) && sfp::aligned16(io->d_vals);
+    s.pov_vec = sfp::aligned16(io->d_pov);
+  }
+  s.probs = io->d_probs, s.value = io->d_value, s.action = io->d_action, s.reward = io->d_reward, s.disc = io->d_disc, s.imitate = io->d_imitate;
+  s.reset_mask = io->d_reset_mask, s.reset_words = io->d_reset_words, s.reset_stride = io->reset_stride;
+  s.reset_group = io->reset_group > 0 ? io->reset_group : 1;
+  s.agents = io->agents;
+  SFP_HIP(hipSetDevice(r->device));
+  hipLaunchKernelGGL(sfp::k_rollout_record, dim3((unsigned)((io->agents + 3) / 4)), dim3(256), 0, r->stream, r->d, s);
+  SFP_HIP(hipGetLastError());
+  return SF_OK;
+}
+
+int sf_rollout_fill_device(sf_rollout *rr, const int32_t **d_fill) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r || !d_fill) return sfp::fail(SF_ERR_ARG, "null argument");
+  *d_fill = r->d.fill;
+  return SF_OK;
+}
+
+int sf_rollout_ready_device(sf_rollout *rr, uint8_t *d_mask) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r || !d_mask) return sfp::fail(SF_ERR_ARG, "null argument");
+  SFP_HIP(hipSetDevice(r->device));
+  hipLaunchKernelGGL(sfp::k_rollout_ready, sfp::per_lane(r->agents), dim3(256), 0, r->stream, r->d.fill, r->d.T, d_mask,
+                     (unsigned long long *)nullptr, r->agents);
+  SFP_HIP(hipGetLastError());
+  return SF_OK;
+}
+
+int sf_rollout_status(sf_rollout *rr, int32_t *ready, int64_t *dropped, int64_t *missing_states) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r) return sfp::fail(SF_ERR_ARG, "null rollout");
+  SFP_HIP(hipSetDevice(r->device));
+  SFP_HIP(hipMemsetAsync(r->d.counters + 2, 0, sizeof(unsigned long long), r->stream));
+  hipLaunchKernelGGL(sfp::k_rollout_ready, sfp::per_lane(r->agents), dim3(256), 0, r->stream, r->d.fill, r->d.T, (uint8_t *)nullptr,
+                     r->d.counters + 2, r->agents);
+  SFP_HIP(hipGetLastError());
+  unsigned long long c[3] = {0, 0, 0};
+  SFP_HIP(hipMemcpyAsync(c, r->d.counters, sizeof(c), hipMemcpyDeviceToHost, r->stream));
+  SFP_HIP(hipStreamSynchronize(r->stream));
+  if (dropped) *dropped = (int64_t)c[0];
+  if (missing_states) *missing_states = (int64_t)c[1];
+  if (ready) *ready = (int32_t)c[2];
+  return SF_OK;
+}
+
+int sf_rollout_returns(sf_rollout *rr, float gamma, float *d_returns, float *d_logv, float *d_adv, float *d_stats) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r) return sfp::fail(SF_ERR_ARG, "null rollout");
+  if (!d_returns && !d_logv && !d_adv && !d_stats) return sfp::fail(SF_ERR_ARG, "null buffer");
+  if (!sfp::aligned16(d_stats)) return sfp::fail(SF_ERR_ARG, "d_stats must be 16-byte aligned");
+  SFP_HIP(hipSetDevice(r->device));
+  hipLaunchKernelGGL(sfp::k_rollout_returns, sfp::per_lane(r->agents), dim3(256), 0, r->stream, r->d, gamma, d_returns, d_logv, d_adv,
+                     d_stats, r->agents);
+  SFP_HIP(hipGetLastError());
+  return SF_OK;
+}
+
+int sf_rollout_release(sf_rollout *rr, const uint8_t *d_mask) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r) return sfp::fail(SF_ERR_ARG, "null rollout");
+  SFP_HIP(hipSetDevice(r->device));
+  hipLaunchKernelGGL(sfp::k_rollout_release, sfp::per_lane(r->agents), dim3(256), 0, r->stream, r->d.fill, r->d.T, d_mask, r->agents);
+  SFP_HIP(hipGetLastError());
+  return SF_OK;
+}
+
+int sf_rollout_state(sf_rollout *rr, int32_t t, const uint32_t **d_keys, const float **d_vals, const uint32_t **d_counts,
+                     const float **d_pov, int32_t *cap) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r || !d_keys || !d_vals || !d_counts || !d_pov || !cap) return sfp::fail(SF_ERR_ARG, "null argument");
+  if (!r->d.keys) return sfp::fail(SF_ERR_STATE, "sf_rollout_state: this rollout keeps no states (keys == NULL at sf_rollout_create)");
+  if (t < 0 || t >= r->d.T) return sfp::fail(SF_ERR_ARG, "slot out of range for this rollout");
+  const size_t row = (size_t)t * (size_t)r->d.stride;
+  *d_keys = r->d.keys + row * r->d.list_cap, *d_vals = r->d.vals + row * r->d.list_cap;
+  *d_counts = r->d.counts + row, *d_pov = r->d.pov + row * sfp::HID, *cap = r->d.list_cap;
+  return SF_OK;
+}
+
+int sf_policy_update_actions(sf_policy *pp, const int32_t *d_action, int32_t agents) {
+  Policy *p = reinterpret_cast<Policy *>(pp);
+  SFP_RC(sfp::check_agents(p, agents));
+  if (!d_action) return sfp::fail(SF_ERR_ARG, "null buffer");
+  SFP_HIP(hipSetDevice(p->device));
+  hipLaunchKernelGGL(sfp::k_update_actions, sfp::per_lane(agents * sfp::ACT), dim3(256), 0, p->stream, p->action_input, d_action, agents);
+  SFP_HIP(hipGetLastError());
   return SF_OK;
 }
 

@@ -156,8 +156,10 @@ def _bind(L):
     L.sf_policy_features.argtypes = [vp, vp, C.c_int32, vp]
     L.sf_policy_kernel_time.argtypes = [vp, C.c_int32, _FP, C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.sf_policy_kernel_time_ex.argtypes = L.sf_policy_kernel_time.argtypes
+    if hasattr(L, "sf_policy_update_actions"):  # (the rollout buffer's replay entry: strikeforce_amd/rollout.py)
+        L.sf_policy_update_actions.argtypes = [vp, vp, C.c_int32]
     for n in EXPORTS + REWARD_EXPORTS:
-        if n != "sf_policy_destroy":
+        if n != "sf_policy_destroy" and hasattr(L, n):
             getattr(L, n).restype = C.c_int
     L._sf_policy_bound = True
 
@@ -167,7 +169,8 @@ EXPORTS = ["sf_policy_create", "sf_policy_destroy", "sf_policy_reset_memory", "s
            "sf_policy_forward_sparse_or_dense",
            "sf_policy_sparse_overflows", "sf_policy_act", "sf_policy_predict_sparse",
            "sf_policy_get_memory", "sf_policy_set_memory", "sf_policy_set_stream", "sf_policy_synchronize",
-           "sf_policy_kernel_time", "sf_policy_kernel_time_ex", "sf_policy_kernel_time_by_kernel", "sf_policy_gemm", "sf_policy_gemm_split", "sf_policy_features", "sf_policy_abi_version"]
+           "sf_policy_kernel_time", "sf_policy_kernel_time_ex", "sf_policy_kernel_time_by_kernel", "sf_policy_gemm", "sf_policy_gemm_split", "sf_policy_features", "sf_policy_abi_version",
+           "sf_policy_update_actions"]
 
 
 # the reward network's entries (sf_reward_*: the same header)
@@ -242,6 +245,11 @@ class _NetBatch:
             self._ck(self.L.sf_policy_reset_memory(self.h, m), "sf_policy_reset_memory")
         else:
             self._ck(self.L.sf_policy_reset_memory_n(self.h, m, int(agents)), "sf_policy_reset_memory_n")
+
+    def update_actions(self, d_action_ptr, agents):
+        """AgentModel::update_actions(one_hot(action)) for agents [0, agents) (device int32 per agent; outside [0, 9): 0):
+        what a replay of a stored rollout calls behind every forward (RolloutBatch)."""
+        self._ck(self.L.sf_policy_update_actions(self.h, C.c_void_p(d_action_ptr), int(agents)), "sf_policy_update_actions")
 
     def sparse_overflows(self):
         """Agents evaluated on an empty observation since the last call because their list did not fit (synchronises)."""

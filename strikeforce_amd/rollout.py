@@ -1,0 +1,175 @@
+"""The device rollout buffer (include/strikeforce_policy.h, sf_rollout_*): bot-1's T-step record, returns and advantages.
+
+One reference `Agent` keeps `states, log_probs, values, rewards, actions` per game (bots/bot-1/Agent.hpp:200-204,227,
+233-234,301-302), fills them for T ticks and then runs computeReturns() (:333-339) and train_log() (:341-351) over them.
+``RolloutBatch`` does that for every agent of a batch behind ``PolicyBatch.predict_sparse`` and
+``RewardBatch.reward_sparse``: it allocates the storage as torch tensors (slot-major, ``[T][agents]...``, exposed as
+attributes), records one tick per call, and hands the learner returns, log V, advantages and the statistics of the agents
+whose buffer is full.  The learners themselves (gradients, AdamW, backups) are the caller's.  No CPU path.
+"""
+import ctypes as C
+
+from . import env, policy
+
+HIDDEN, ACTIONS = policy.HIDDEN, policy.ACTIONS
+
+# every sf_rollout_* symbol include/strikeforce_policy.h declares (sf_policy_update_actions is in policy.EXPORTS)
+EXPORTS = ["sf_rollout_create", "sf_rollout_destroy", "sf_rollout_set_stream", "sf_rollout_synchronize", "sf_rollout_record",
+           "sf_rollout_fill_device", "sf_rollout_ready_device", "sf_rollout_status", "sf_rollout_returns", "sf_rollout_release",
+           "sf_rollout_state"]
+
+
+class Buffers(C.Structure):
+    """sf_rollout_buffers."""
+    _fields_ = [("keys", C.c_void_p), ("vals", C.c_void_p), ("counts", C.c_void_p), ("pov", C.c_void_p), ("action", C.c_void_p),
+                ("logp", C.c_void_p), ("value", C.c_void_p), ("reward", C.c_void_p), ("disc", C.c_void_p), ("imitate", C.c_void_p)]
+
+
+class Step(C.Structure):
+    """sf_rollout_step."""
+    _fields_ = [("d_keys", C.c_void_p), ("d_vals", C.c_void_p), ("d_counts", C.c_void_p), ("d_pov", C.c_void_p), ("cap", C.c_int32),
+                ("agents", C.c_int32), ("d_probs", C.c_void_p), ("d_value", C.c_void_p), ("d_action", C.c_void_p),
+                ("d_reward", C.c_void_p), ("d_disc", C.c_void_p), ("d_imitate", C.c_void_p), ("d_reset_mask", C.c_void_p),
+                ("d_reset_words", C.c_void_p), ("reset_stride", C.c_int32), ("reset_group", C.c_int32)]
+
+
+def _bind(L):
+    if getattr(L, "_sf_rollout_bound", False):
+        return
+    vp, pp = C.c_void_p, C.POINTER(C.c_void_p)
+    L.sf_rollout_create.argtypes = [C.POINTER(Buffers), C.c_int32, C.c_int32, C.c_int32, C.c_int32, pp]
+    L.sf_rollout_destroy.argtypes = [vp]
+    L.sf_rollout_destroy.restype = None
+    L.sf_rollout_set_stream.argtypes = [vp, vp]
+    L.sf_rollout_synchronize.argtypes = [vp]
+    L.sf_rollout_record.argtypes = [vp, C.POINTER(Step)]
+    L.sf_rollout_fill_device.argtypes = [vp, pp]
+    L.sf_rollout_ready_device.argtypes = [vp, vp]
+    L.sf_rollout_status.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.sf_rollout_returns.argtypes = [vp, C.c_float, vp, vp, vp, vp]
+    L.sf_rollout_release.argtypes = [vp, vp]
+    L.sf_rollout_state.argtypes = [vp, C.c_int32, pp, pp, pp, pp, C.POINTER(C.c_int32)]
+    for n in EXPORTS:
+        if n != "sf_rollout_destroy":
+            getattr(L, n).restype = C.c_int
+    L._sf_rollout_bound = True
+
+
+class RolloutBatch:
+    """The five vectors of `agents` reference Agents, T slots each.  Tensors (device, slot-major): keys, vals
+    [T][agents][list_cap], counts [T][agents], pov [T][agents][160] (None with store_states=False), action [T][agents]
+    int32, logp [T][agents][9], value, reward [T][agents], disc [T][agents] and imitate [T][agents] uint8 (None unless
+    asked for)."""
+
+    def __init__(self, agents, T, list_cap, store_states=True, store_disc=False, store_imitate=False, device=0):
+        import torch
+        self.L = env.load_library()
+        if not hasattr(self.L, "sf_rollout_create"):
+            raise env.StrikeForceError("libstrikeforce_amd.so has no rollout buffer: rebuild it (python -m strikeforce_amd.build)")
+        _bind(self.L)
+        self.agents, self.T, self.list_cap = int(agents), int(T), int(list_cap)
+        self.h = None
+        if torch.cuda.is_available() and self.agents >= 1 and self.T >= 1 and self.list_cap >= 1:
+            dev = torch.device("cuda", int(device))
+            new = lambda shape, dtype: torch.zeros((self.T, self.agents) + shape, dtype=dtype, device=dev)
+            f32, i32 = torch.float32, torch.int32
+            self.keys = new((self.list_cap,), i32) if store_states else None
+            self.vals = new((self.list_cap,), f32) if store_states else None
+            self.counts = new((), i32) if store_states else None
+            self.pov = new((HIDDEN,), f32) if store_states else None
+            self.action, self.logp, self.value, self.reward = new((), i32), new((ACTIONS,), f32), new((), f32), new((), f32)
+            self.disc = new((), f32) if store_disc else None
+            self.imitate = new((), torch.uint8) if store_imitate else None
+            ptr = lambda t: t.data_ptr() if t is not None else None
+        else:  # (no device, or sizes no tensor can have: the library says which — SF_ERR_DEVICE / SF_ERR_ARG)
+            self.keys = self.vals = self.counts = self.pov = self.disc = self.imitate = None
+            self.action = self.logp = self.value = self.reward = None
+            ptr, dev = (lambda t: None), None
+        b = Buffers(ptr(self.keys), ptr(self.vals), ptr(self.counts), ptr(self.pov), ptr(self.action), ptr(self.logp), ptr(self.value),
+                    ptr(self.reward), ptr(self.disc), ptr(self.imitate))
+        h = C.c_void_p()
+        rc = self.L.sf_rollout_create(C.byref(b), self.agents, self.T, self.list_cap, int(device), C.byref(h))
+        if rc != 0:
+            raise env.StrikeForceError("sf_rollout_create failed (%d): %s" % (rc, self.L.sf_last_error().decode()))
+        self.h = h
+        self._torch, self._dev = torch, dev
+
+    def _ck(self, rc, what):
+        if rc != 0:
+            raise env.StrikeForceError("%s failed (%d): %s" % (what, rc, self.L.sf_last_error().decode()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.sf_rollout_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        self._ck(self.L.sf_rollout_set_stream(self.h, C.c_void_p(hip_stream)), "sf_rollout_set_stream")
+
+    def synchronize(self):
+        self._ck(self.L.sf_rollout_synchronize(self.h), "sf_rollout_synchronize")
+
+    def record(self, d_probs_ptr, d_value_ptr, d_action_ptr, d_reward_ptr, d_keys_ptr=None, d_vals_ptr=None, d_counts_ptr=None,
+               d_pov_ptr=None, cap=0, agents=None, d_disc_ptr=None, d_imitate_ptr=None, d_reset_mask_ptr=None, reset_words=None):
+        """One tick: PolicyBatch.predict_sparse's probabilities, value and action, RewardBatch.reward_sparse's reward (and D),
+        the observation lists both read, and the restart flags both were given.  One launch on this object's stream."""
+        io = Step()
+        io.d_keys, io.d_vals, io.d_counts, io.d_pov, io.cap = d_keys_ptr, d_vals_ptr, d_counts_ptr, d_pov_ptr, int(cap)
+        io.agents = self.agents if agents is None else int(agents)
+        io.d_probs, io.d_value, io.d_action, io.d_reward = d_probs_ptr, d_value_ptr, d_action_ptr, d_reward_ptr
+        io.d_disc, io.d_imitate, io.d_reset_mask = d_disc_ptr, d_imitate_ptr, d_reset_mask_ptr
+        if reset_words is not None:
+            io.d_reset_words, io.reset_stride, io.reset_group = reset_words
+        self._ck(self.L.sf_rollout_record(self.h, C.byref(io)), "sf_rollout_record")
+
+    def fill(self):
+        """The cursors as a device tensor view (int32 per agent, the library's memory: read it, do not write it)."""
+        p = C.c_void_p()
+        self._ck(self.L.sf_rollout_fill_device(self.h, C.byref(p)), "sf_rollout_fill_device")
+        if not hasattr(self, "_fill"):
+            iface = {"shape": (self.agents,), "typestr": "<i4", "data": (p.value, False), "version": 2}
+            holder = type("FillView", (), {"__cuda_array_interface__": iface})()
+            self._fill = self._torch.as_tensor(holder, device=self._dev)
+        return self._fill
+
+    def ready_mask(self, out=None):
+        """uint8 per agent, 1 = its buffer is full: what reset_memory and release take."""
+        if out is None:
+            out = self._torch.empty(self.agents, dtype=self._torch.uint8, device=self._dev)
+        self._ck(self.L.sf_rollout_ready_device(self.h, C.c_void_p(out.data_ptr())), "sf_rollout_ready_device")
+        return out
+
+    def status(self):
+        """(ready agents now, ticks dropped on ready agents, states stored with a list that did not fit); synchronises."""
+        r, d, m = C.c_int32(), C.c_int64(), C.c_int64()
+        self._ck(self.L.sf_rollout_status(self.h, C.byref(r), C.byref(d), C.byref(m)), "sf_rollout_status")
+        return r.value, d.value, m.value
+
+    def returns(self, gamma=0.99, out=None):
+        """computeReturns(), log V, the advantage and train_log()'s four numbers for the ready agents: (returns, logv, adv
+        [T][agents], stats [agents][4]).  Rows of agents that are not ready are not written (new tensors hold NaN there)."""
+        t = self._torch
+        if out is None:
+            nan = lambda shape: t.full(shape, float("nan"), dtype=t.float32, device=self._dev)
+            out = (nan((self.T, self.agents)), nan((self.T, self.agents)), nan((self.T, self.agents)), nan((self.agents, 4)))
+        self._ck(self.L.sf_rollout_returns(self.h, C.c_float(gamma), *[C.c_void_p(x.data_ptr()) if x is not None else None for x in out]),
+                 "sf_rollout_returns")
+        return out
+
+    def release(self, mask=None):
+        """clear(): every ready agent starts at slot 0 again; with a mask (device uint8 per agent, or its address), the agents
+        it names, ready or not."""
+        m = None if mask is None else C.c_void_p(mask if isinstance(mask, int) else mask.data_ptr())
+        self._ck(self.L.sf_rollout_release(self.h, m), "sf_rollout_release")
+
+    def state(self, t):
+        """(d_keys, d_vals, d_counts, d_pov, cap) of slot t: the leading arguments of forward_sparse / reward_sparse."""
+        k, v, c, p, cap = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        self._ck(self.L.sf_rollout_state(self.h, int(t), C.byref(k), C.byref(v), C.byref(c), C.byref(p), C.byref(cap)), "sf_rollout_state")
+        return k.value, v.value, c.value, p.value, cap.value
