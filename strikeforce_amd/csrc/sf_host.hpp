@@ -48,6 +48,20 @@ inline int host_compute_damage(int x, int y) {
   return l;
 }
 
+// The generator's tables (sf_types.hpp LOGT_*, Params::logt / exptab): discrete logs and powers of the generator 3 of
+// Z/65537*.  logt[LOGT_ENTRIES] must come in zeroed (the entries of residue 0 stay 0), exptab holds 512 words.  A function
+// of its own so that tests/wave_probe checks the very tables the product uploads.
+inline void build_rng_tables(uint16_t *logt, uint32_t *exptab) {
+  uint32_t v = 1;
+  for (uint32_t m = 0; m < 65536; ++m) {
+    logt[LOGT_OFF + v] = (uint16_t)m;                                              // t = v
+    if (v + (uint32_t)LOGT_OFF >= 65537u) logt[LOGT_OFF + v - 65537u] = (uint16_t)m;  // t = v - 65537 < 0
+    if (m < 256) exptab[m] = v;
+    if ((m & 255u) == 0) exptab[256 + (m >> 8)] = v;
+    v = (uint32_t)(((uint64_t)v * 3u) % 65537u);
+  }
+}
+
 // Human::build, Character.hpp:650-709: what a freshly built human of this profile carries.
 inline void derive_profile(const sf_config &cfg, const sf_profile &pr, Derived &d) {
   int def_blocks = 8, def_portals = 1;  // Character.hpp:78-79
@@ -355,16 +369,7 @@ struct Env {
     // RNG tables: discrete logs / powers of the generator 3 of Z/65537*
     std::vector<uint16_t> logt(LOGT_ENTRIES, 0);
     std::vector<uint32_t> exptab(512);
-    {
-      uint32_t v = 1;
-      for (uint32_t m = 0; m < 65536; ++m) {
-        logt[LOGT_OFF + v] = (uint16_t)m;                                              // t = v
-        if (v + (uint32_t)LOGT_OFF >= 65537u) logt[LOGT_OFF + v - 65537u] = (uint16_t)m;  // t = v - 65537 < 0
-        if (m < 256) exptab[m] = v;
-        if ((m & 255u) == 0) exptab[256 + (m >> 8)] = v;
-        v = (uint32_t)(((uint64_t)v * 3u) % 65537u);
-      }
-    }
+    build_rng_tables(logt.data(), exptab.data());
     // device state
     const size_t A = (size_t)p.A;
     if ((rc = alloc(d_logt, (size_t)LOGT_ENTRIES)) || (rc = alloc(d_exptab, 512)) || (rc = alloc(d_tab, 1)) || (rc = alloc(d_map_flags, (size_t)p.cells_pad)) || (rc = alloc(d_map_pidx, (size_t)cells)) ||
