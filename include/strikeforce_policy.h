@@ -345,6 +345,46 @@ int sf_rollout_state(sf_rollout *r, int32_t t, const uint32_t **d_keys, const fl
  * the state of slot t, then this call on action[t] — reproduces every ready agent's sequence. */
 int sf_policy_update_actions(sf_policy *p, const int32_t *d_action, int32_t agents);
 
+/* ---- parameters in: what a learner hands back ---------------------------------------------------------------------------
+ * The parameters the next forward sees are these (optimizer->step(), bots/bot-1/Agent.hpp:415-417, then model->forward,
+ * :202; RewardNet::train_epoch does the same to the discriminator, :428): d_w holds DEVICE pointers, same fields / shapes /
+ * torch layouts as for sf_policy_create.  Works on a policy and on a reward model (policy_* fields not looked at there).
+ *
+ * Images refreshed.  Every image sf_policy_create derives is derived again, in the form the object was created in (folded
+ *   or layered, fused tail or not, f32-conv, dense-conv0: the environment switches are NOT read again): conv0's weights and
+ *   their transpose, the permuted conv1..3, the bf16-split images of conv1 and conv2, the composed matrix F; the GRU
+ *   matrices and biases, the padded combined_processor; the ResB layers, the heads and their 16-row paddings; k_tail's whole
+ *   weight block in its stream order.
+ * Bit for bit.  After the call every image holds bit for bit what sf_policy_create would have put there for the same
+ *   parameters; pad regions stay zero.  (Parameters are finite: a NaN the bf16 split makes of an infinity has no
+ *   specified sign.)
+ * Stream order.  All work is launched on the object's stream (sf_policy_set_stream), the composition of F too.  A forward
+ *   issued before the call sees the old parameters, one issued after it the new ones; no host synchronisation is needed
+ *   between them.  The sources are read in stream order and must stay valid and unchanged until the stream has passed the
+ *   call.
+ * Allocation and synchronisation.  The first call on an object in the folded form allocates the composition's f64 workspace,
+ *   97.3 MB, and keeps it until sf_policy_destroy (layered form: nothing).  Later calls allocate nothing; no call
+ *   synchronises.
+ * State left alone.  Per-agent memory (h, action_input), stream, timers and the overflow counter are untouched: the caller
+ *   calls sf_policy_reset_memory as Agent.hpp:432 does.
+ * Validation.  Everything is validated before the first launch, and a failed call leaves the object exactly as it was:
+ *   SF_ERR_ARG for a NULL object or struct, an abi_version mismatch, a NULL field this kind of object needs, a pointer that
+ *   is not 4-byte aligned, a pointer that is not device memory of the object's device (hipPointerGetAttributes), or one
+ *   whose extent — the field's float count — does not lie inside its allocation (hipMemGetAddressRange).  A host pointer
+ *   handed to a kernel would fault the device: that is what the guard is for.
+ * Alignment.  Sources need only 4-byte alignment (parameters carved out of one flat tensor). */
+int sf_policy_load_weights(sf_policy *p, const sf_policy_weights *d_w);
+
+/* Test hook: one 64-bit digest per device image the object derives from its parameters, over the WHOLE allocation of each
+ * (pads included), into out_host.  *count in: capacity, out: how many (SF_ERR_ARG if the capacity is too small; 40 is
+ * enough).  Order: conv0's weights, their transpose, the permuted conv1, conv2, conv3, the split images of conv1 and conv2,
+ * F (folded form only: the layered form has one entry less); per GRU cell g = 0, 1: weight_ih, weight_hh, bias_ih, bias_hh;
+ * combined_processor's padded weight, its bias; per head (a policy: policy, value; a reward model: value) the three ResB
+ * weights, the three ResB biases, the output weight, its bias, the 16-row weight, the 16-row bias; k_tail's block.  39
+ * entries for a folded policy, 29 for a folded reward model.  A digest is the sum mod 2^64 of a position-keyed mix of the
+ * image's 32-bit words: equal images give equal digests, on any object.  Synchronises the object's stream. */
+int sf_policy_weights_digest(sf_policy *p, uint64_t *out_host, int32_t *count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,7 +24,8 @@
 //                         residual blocks' relu+skip and the two heads.
 //
 // The kernels are in sf_policy_gemm.hpp, sf_policy_conv.hpp and sf_policy_tail.hpp; the weight layouts that the host
-// prepares for them are in sf_policy_stage.hpp (no HIP: tested on the CPU).  This file is the host side and the C ABI.
+// prepares for them are in sf_policy_stage.hpp (no HIP: tested on the CPU).  sf_policy_load.hpp builds the same layouts on
+// the device from device pointers (sf_policy_load_weights).  This file is the host side and the C ABI.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -98,6 +99,10 @@ struct Policy {
   float *feat = nullptr, *feat_n = nullptr, *gi = nullptr, *gh = nullptr, *comb = nullptr, *gated = nullptr,
         *gated_n = nullptr, *out = nullptr, *x[2] = {}, *lin[2] = {};
   std::vector<void *> owned;
+  // sf_policy_load_weights: the fold's f64 workspace (allocated by the first load of a folded object, in `owned`);
+  // sf_policy_weights_digest: its result buffer (allocated by the first query)
+  double *fold_ws[4] = {};
+  unsigned long long *d_digest = nullptr;
   // timing of the matrix launches: an event pair and a kind per launch, the flop per kind.  Kinds: 0 k_gemm (f32 MFMA),
   // 1 k_gemm_b3 (bf16 split), 2 the convolutions on the non-zeros (k_feat_*, k_conv0_sparse<true>), 3 k_tail
   bool timing = false;
@@ -537,6 +542,8 @@ static int forward(Policy *p, int agents, const ForwardReq &r) {
 
 }  // namespace sfp
 
+#include "sf_policy_load.hpp"
+
 using sfp::Policy;
 
 extern "C" {
@@ -952,6 +959,14 @@ int sf_policy_update_actions(sf_policy *pp, const int32_t *d_action, int32_t age
   hipLaunchKernelGGL(sfp::k_update_actions, sfp::per_lane(agents * sfp::ACT), dim3(256), 0, p->stream, p->action_input, d_action, agents);
   SFP_HIP(hipGetLastError());
   return SF_OK;
+}
+
+int sf_policy_load_weights(sf_policy *pp, const sf_policy_weights *d_w) {
+  return sfp::load_weights(reinterpret_cast<Policy *>(pp), d_w);
+}
+
+int sf_policy_weights_digest(sf_policy *pp, uint64_t *out_host, int32_t *count) {
+  return sfp::weights_digest(reinterpret_cast<Policy *>(pp), out_host, count);
 }
 
 }  // extern "C"

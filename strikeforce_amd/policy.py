@@ -111,6 +111,60 @@ def load_checkpoint(path):
     return out
 
 
+def _fill_weights(ptr, shapes):
+    """A Weights whose fields are ptr(name) for the parameter names of `shapes` (a reward model's table has no policy.*
+    names: those fields stay NULL)."""
+    w = Weights()
+    w.abi_version = POLICY_ABI_VERSION
+    for i in range(CONVS):
+        w.conv_w[i] = ptr("backbone.cnn.conv%d.weight" % i)
+    for g in range(2):
+        w.gru_w_ih[g] = ptr("backbone.gru%d.weight_ih_l0" % g)
+        w.gru_w_hh[g] = ptr("backbone.gru%d.weight_hh_l0" % g)
+        w.gru_b_ih[g] = ptr("backbone.gru%d.bias_ih_l0" % g)
+        w.gru_b_hh[g] = ptr("backbone.gru%d.bias_hh_l0" % g)
+    w.comb_w, w.comb_b = ptr("backbone.combined_processor.0.weight"), ptr("backbone.combined_processor.0.bias")
+    for i in range(RES_LAYERS):
+        w.value_res_w[i], w.value_res_b[i] = ptr("value.0.lin%d.weight" % i), ptr("value.0.lin%d.bias" % i)
+    w.value_w, w.value_b = ptr("value.1.weight"), ptr("value.1.bias")
+    if "policy.1.weight" in shapes:
+        for i in range(RES_LAYERS):
+            w.policy_res_w[i], w.policy_res_b[i] = ptr("policy.0.lin%d.weight" % i), ptr("policy.0.lin%d.bias" % i)
+        w.policy_w, w.policy_b = ptr("policy.1.weight"), ptr("policy.1.bias")
+    return w
+
+
+def device_weights(tensors, shapes):
+    """The `Weights` of sf_policy_load_weights for parameters that live on the device: `tensors` is a dict of torch tensors
+    keyed by the reference's parameter names, `shapes` the kind's table (`parameter_shapes()` / `reward_parameter_shapes()`;
+    names outside it are ignored).  Every tensor named there must be a contiguous float32 tensor of that shape on one and
+    the same GPU — views into one flat tensor are fine, any 4-byte offset will do — or this raises ValueError naming the
+    parameter; nothing is converted or copied.  Returns (weights, keep): `keep` holds the tensors the pointers point into
+    and must outlive every load issued with `weights`, until the stream has passed it."""
+    import torch
+    keep, device = {}, None
+    for name, shape in shapes.items():
+        if name not in tensors:
+            raise ValueError("missing parameter %s" % name)
+        t = tensors[name]
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("parameter %s is a %s, not a torch tensor" % (name, type(t).__name__))
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError("parameter %s has shape %s, expected %s" % (name, tuple(t.shape), tuple(shape)))
+        if t.dtype != torch.float32:
+            raise ValueError("parameter %s has dtype %s, expected torch.float32" % (name, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError("parameter %s is not contiguous" % name)
+        if t.device.type != "cuda":
+            raise ValueError("parameter %s is on %s, not on a GPU" % (name, t.device))
+        if device is None:
+            device = t.device
+        elif t.device != device:
+            raise ValueError("parameter %s is on %s, the parameters before it on %s" % (name, t.device, device))
+        keep[name] = t
+    return _fill_weights(lambda n: C.cast(C.c_void_p(keep[n].data_ptr()), _FP), shapes), keep
+
+
 class PredictIO(C.Structure):
     """sf_policy_predict_io (include/strikeforce_policy.h)."""
     _fields_ = [("d_keys", C.c_void_p), ("d_vals", C.c_void_p), ("d_counts", C.c_void_p), ("d_pov", C.c_void_p), ("cap", C.c_int32),
@@ -158,6 +212,9 @@ def _bind(L):
     L.sf_policy_kernel_time_ex.argtypes = L.sf_policy_kernel_time.argtypes
     if hasattr(L, "sf_policy_update_actions"):  # (the rollout buffer's replay entry: strikeforce_amd/rollout.py)
         L.sf_policy_update_actions.argtypes = [vp, vp, C.c_int32]
+    if hasattr(L, "sf_policy_load_weights"):  # (parameters in, from the device: _NetBatch.load_weights)
+        L.sf_policy_load_weights.argtypes = [vp, C.POINTER(Weights)]
+        L.sf_policy_weights_digest.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
     for n in EXPORTS + REWARD_EXPORTS:
         if n != "sf_policy_destroy" and hasattr(L, n):
             getattr(L, n).restype = C.c_int
@@ -170,7 +227,7 @@ EXPORTS = ["sf_policy_create", "sf_policy_destroy", "sf_policy_reset_memory", "s
            "sf_policy_sparse_overflows", "sf_policy_act", "sf_policy_predict_sparse",
            "sf_policy_get_memory", "sf_policy_set_memory", "sf_policy_set_stream", "sf_policy_synchronize",
            "sf_policy_kernel_time", "sf_policy_kernel_time_ex", "sf_policy_kernel_time_by_kernel", "sf_policy_gemm", "sf_policy_gemm_split", "sf_policy_features", "sf_policy_abi_version",
-           "sf_policy_update_actions"]
+           "sf_policy_update_actions", "sf_policy_load_weights", "sf_policy_weights_digest"]
 
 
 # the reward network's entries (sf_reward_*: the same header)
@@ -183,7 +240,7 @@ class _NetBatch:
     def __init__(self, params, max_agents, device, shapes, create):
         self.L = env.load_library()
         _bind(self.L)
-        self.max_agents = int(max_agents)
+        self.max_agents, self.device, self.shapes = int(max_agents), int(device), shapes
         keep = {}
         for name, shape in shapes.items():
             if name not in params:
@@ -192,24 +249,7 @@ class _NetBatch:
             if a.shape != tuple(shape):
                 raise ValueError("parameter %s has shape %s, expected %s" % (name, a.shape, shape))
             keep[name] = a
-        ptr = lambda n: keep[n].ctypes.data_as(_FP)
-        w = Weights()
-        w.abi_version = POLICY_ABI_VERSION
-        for i in range(CONVS):
-            w.conv_w[i] = ptr("backbone.cnn.conv%d.weight" % i)
-        for g in range(2):
-            w.gru_w_ih[g] = ptr("backbone.gru%d.weight_ih_l0" % g)
-            w.gru_w_hh[g] = ptr("backbone.gru%d.weight_hh_l0" % g)
-            w.gru_b_ih[g] = ptr("backbone.gru%d.bias_ih_l0" % g)
-            w.gru_b_hh[g] = ptr("backbone.gru%d.bias_hh_l0" % g)
-        w.comb_w, w.comb_b = ptr("backbone.combined_processor.0.weight"), ptr("backbone.combined_processor.0.bias")
-        for i in range(RES_LAYERS):
-            w.value_res_w[i], w.value_res_b[i] = ptr("value.0.lin%d.weight" % i), ptr("value.0.lin%d.bias" % i)
-        w.value_w, w.value_b = ptr("value.1.weight"), ptr("value.1.bias")
-        if "policy.1.weight" in shapes:  # (a reward model has no policy head: those fields stay NULL)
-            for i in range(RES_LAYERS):
-                w.policy_res_w[i], w.policy_res_b[i] = ptr("policy.0.lin%d.weight" % i), ptr("policy.0.lin%d.bias" % i)
-            w.policy_w, w.policy_b = ptr("policy.1.weight"), ptr("policy.1.bias")
+        w = _fill_weights(lambda n: keep[n].ctypes.data_as(_FP), shapes)
         self.h = C.c_void_p()
         rc = getattr(self.L, create)(C.byref(w), self.max_agents, int(device), C.byref(self.h))
         if rc != 0:
@@ -250,6 +290,26 @@ class _NetBatch:
         """AgentModel::update_actions(one_hot(action)) for agents [0, agents) (device int32 per agent; outside [0, 9): 0):
         what a replay of a stored rollout calls behind every forward (RolloutBatch)."""
         self._ck(self.L.sf_policy_update_actions(self.h, C.c_void_p(d_action_ptr), int(agents)), "sf_policy_update_actions")
+
+    def load_weights(self, tensors):
+        """optimizer->step() seen from the device (sf_policy_load_weights): the parameters every later forward on this
+        object's stream uses are `tensors` — torch tensors on this object's GPU, checked by `device_weights` against the
+        kind's shape table.  Stream-ordered, no synchronisation; per-agent memory, stream and timers stay as they are.
+        The tensors are read when the stream gets there: they are kept alive here until the next load, and work that
+        changes them has to be ordered behind this call (issued later on the same stream, or after a synchronise)."""
+        w, keep = device_weights(tensors, self.shapes)
+        for name, t in keep.items():
+            if t.device.index != self.device:
+                raise ValueError("parameter %s is on %s, this object on device %d" % (name, t.device, self.device))
+        self._ck(self.L.sf_policy_load_weights(self.h, C.byref(w)), "sf_policy_load_weights")
+        self._loaded = keep
+
+    def weights_digest(self):
+        """One 64-bit digest per device image the object derives from its parameters, in the header's order (test hook;
+        synchronises)."""
+        out, n = (C.c_uint64 * 64)(), C.c_int32(64)
+        self._ck(self.L.sf_policy_weights_digest(self.h, out, C.byref(n)), "sf_policy_weights_digest")
+        return [int(out[i]) for i in range(n.value)]
 
     def sparse_overflows(self):
         """Agents evaluated on an empty observation since the last call because their list did not fit (synchronises)."""
