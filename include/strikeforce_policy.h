@@ -385,6 +385,83 @@ int sf_policy_load_weights(sf_policy *p, const sf_policy_weights *d_w);
  * image's 32-bit words: equal images give equal digests, on any object.  Synchronises the object's stream. */
 int sf_policy_weights_digest(sf_policy *p, uint64_t *out_host, int32_t *count);
 
+/* ---- several networks in one match: routing agents to parameter sets ----------------------------------------------------
+ * In the reference every commanded human owns its network: gameplay::prepare does `player.agent = new Agent`
+ * (bots/bot-0.5/Custom.hpp:161-165), the constructor loads that agent's own backup_dir/model.pt (bots/bot-1/Agent.hpp:84-101),
+ * and every seat of an online Battle is a client of its own, built with its own bot and holding its own checkpoint
+ * (gameplay.hpp:57-207, selected_agent.hpp:25): that is how two bots, or two checkpoints of one, meet in one match.  An
+ * sf_policy has ONE parameter set and evaluates rows [0, agents) of the buffers it is given.  An sf_route is the static
+ * assignment of an environment's agents to up to SF_ROUTE_MAX_NETS such objects: sf_route_gather copies each network's
+ * agents into rows of that network's own, sf_route_scatter copies the results back into the environment's order, both on
+ * the device in stream order with no host work per tick.  Between them every entry above (sf_policy_predict_sparse,
+ * sf_reward_sparse, sf_rollout_record, sf_policy_load_weights) works per network, unchanged, on count(k) rows.
+ *
+ * Slots.  Agent a of network k = assign[a] gets slot s = its rank among k's agents in ascending a.  The mapping never
+ *   changes, so slot s of network k is one agent's h_state / action_input for the whole run (one `Agent` object).
+ * Action draws.  sf_policy_predict_sparse keys its draw by the row it sees: behind a route, draw i of slot s is the hash of
+ *   (seed, s, i), not of (seed, a, i).  Give every network a seed of its own, or slot s of two networks draws alike. */
+#define SF_ROUTE_MAX_NETS 8
+typedef struct sf_route sf_route;
+
+/* assign (host, [agents]): assign[a] in [0, nets), or -1 for nobody's — a scripted, random or remote player (Custom.hpp:
+ * 161-165 only builds an Agent for a commanded human).  SF_ERR_ARG: a NULL pointer, agents outside [1, 1048576], nets
+ * outside [1, SF_ROUTE_MAX_NETS], an assign[a] outside [-1, nets).  The object owns two small device tables: (net, slot) per
+ * agent, and the agent per (net, slot). */
+int sf_route_create(const int32_t *assign, int32_t agents, int32_t nets, int32_t device, sf_route **out);
+void sf_route_destroy(sf_route *r);
+int sf_route_set_stream(sf_route *r, void *hip_stream);
+int sf_route_synchronize(sf_route *r);
+/* *n = how many agents network `net` has (a network may have none); *d_agent_of_slot = its agents by slot (device, int32
+ * [count], the library's; valid until sf_route_destroy).  SF_ERR_ARG for net outside [0, nets). */
+int sf_route_count(sf_route *r, int32_t net, int32_t *n);
+int sf_route_agents_device(sf_route *r, int32_t net, const int32_t **d_agent_of_slot);
+
+/* One tick's observation, environment order, exactly as sf_policy_predict_io takes it (the state every Agent::predict() of
+ * the tick is handed, Agent.hpp:200-201), and one network's rows of it: the caller's storage, count(k) rows. */
+typedef struct sf_route_src {
+  const uint32_t *d_keys;
+  const float *d_vals;
+  const uint32_t *d_counts;
+  const float *d_pov;
+  int32_t cap;
+  const float *d_dense;          /* optional: [agents][32][31][31], rows of the agents whose list did not fit */
+  const uint8_t *d_reset_mask;   /* optional, one byte per agent */
+  const int32_t *d_reset_words;  /* optional: agent a reads word (a / reset_group) * reset_stride */
+  int32_t reset_stride, reset_group;
+} sf_route_src;
+typedef struct sf_route_dst {
+  uint32_t *d_keys; /* [n_k][cap] */
+  float *d_vals;    /* [n_k][cap] */
+  uint32_t *d_counts;
+  float *d_pov;     /* [n_k][160] */
+  int32_t cap;      /* the source's cap (SF_ERR_ARG otherwise) */
+  float *d_dense;   /* optional: [n_k][32][31][31] */
+  uint8_t *d_reset_mask; /* optional: [n_k] bytes, what sf_policy_predict_io.d_reset_mask takes */
+} sf_route_dst;
+/* ONE launch for all networks (dst[nets] travels in the kernel arguments; nothing is allocated or copied ahead of it).  Per
+ * assigned agent, into row `slot` of its network: min(count, cap) list entries — nothing behind the count is written; the
+ * count as it came, the 0xffffffff marker included, so that "did not fit" means to the network what it meant to the
+ * environment; the 160 pov floats; the restart flag as one byte (a non-zero source byte or word gives 1, else 0: gameplay.hpp:
+ * 481, a new Agent per game); the dense row ONLY for an agent whose list did not fit, and only if both src->d_dense and
+ * dst[k].d_dense are given.  A network without agents, or a dst[k] whose pointers are all NULL, is skipped.  Copies are
+ * 16 bytes wide where cap % 4 == 0 and both bases are 16-byte aligned, dwords otherwise.  SF_ERR_ARG: NULL r, src or dst; a
+ * NULL list pointer or a cap outside [1, SF_POLICY_LIST_MAX] in src; a dst[k] that is neither complete (d_keys, d_vals,
+ * d_counts, d_pov) nor all NULL, or whose cap differs from src->cap. */
+int sf_route_gather(sf_route *r, const sf_route_src *src, const sf_route_dst *dst);
+
+/* What the networks answered (Agent::predict()'s outputs and get_reward()'s, Agent.hpp:202-204, 227; the command char of
+ * gameplay::bot, Custom.hpp:160-163): rows[k] is network k's compact storage, count(k) rows; env the environment-order
+ * buffers of the same names, [agents] rows.  d_probs is [.][9].  Any pointer may be NULL on either side: that field is
+ * skipped. */
+typedef struct sf_route_rows {
+  uint8_t *d_cmd;
+  int32_t *d_action;
+  float *d_probs, *d_value, *d_reward, *d_disc;
+} sf_route_rows;
+/* ONE launch for all networks: row a of every env buffer = row `slot` of the same-named buffer of a's network.  Rows of the
+ * agents assigned to -1 are not touched: a scripted command the caller put into env->d_cmd survives. */
+int sf_route_scatter(sf_route *r, const sf_route_rows *rows, const sf_route_rows *env);
+
 #ifdef __cplusplus
 }
 #endif

@@ -970,3 +970,5 @@ int sf_policy_weights_digest(sf_policy *pp, uint64_t *out_host, int32_t *count) 
 }
 
 }  // extern "C"
+
+#include "sf_policy_route.hpp"

@@ -438,3 +438,180 @@ class RewardBatch(_NetBatch):
             io.d_reset_words, io.reset_stride, io.reset_group = reset_words
         io.d_action, io.d_disc, io.d_reward = d_action_ptr, d_disc_ptr, d_reward_ptr
         self._ck(self.L.sf_reward_sparse(self.h, C.byref(io), int(agents)), "sf_reward_sparse")
+
+
+# ---- several networks in one match (include/strikeforce_policy.h, sf_route_*) -------------------------------------------------
+ROUTE_MAX_NETS = 8
+ROUTE_EXPORTS = ["sf_route_create", "sf_route_destroy", "sf_route_set_stream", "sf_route_synchronize", "sf_route_count",
+                 "sf_route_agents_device", "sf_route_gather", "sf_route_scatter"]
+ROUTE_ROW_FIELDS = ("cmd", "action", "probs", "value", "reward", "disc")
+
+
+class RouteSrc(C.Structure):
+    """sf_route_src."""
+    _fields_ = [("d_keys", C.c_void_p), ("d_vals", C.c_void_p), ("d_counts", C.c_void_p), ("d_pov", C.c_void_p), ("cap", C.c_int32),
+                ("d_dense", C.c_void_p), ("d_reset_mask", C.c_void_p), ("d_reset_words", C.c_void_p),
+                ("reset_stride", C.c_int32), ("reset_group", C.c_int32)]
+
+
+class RouteDst(C.Structure):
+    """sf_route_dst."""
+    _fields_ = [("d_keys", C.c_void_p), ("d_vals", C.c_void_p), ("d_counts", C.c_void_p), ("d_pov", C.c_void_p), ("cap", C.c_int32),
+                ("d_dense", C.c_void_p), ("d_reset_mask", C.c_void_p)]
+
+
+class RouteRows(C.Structure):
+    """sf_route_rows."""
+    _fields_ = [("d_cmd", C.c_void_p), ("d_action", C.c_void_p), ("d_probs", C.c_void_p), ("d_value", C.c_void_p),
+                ("d_reward", C.c_void_p), ("d_disc", C.c_void_p)]
+
+
+def _bind_route(L):
+    if getattr(L, "_sf_route_bound", False):
+        return
+    if not hasattr(L, "sf_route_create"):  # (an older build loaded through SF_LIBRARY_PATH lacks it)
+        raise env.StrikeForceError("libstrikeforce_amd.so has no sf_route_* entry points: rebuild it (python -m strikeforce_amd.build)")
+    vp, pp = C.c_void_p, C.POINTER(C.c_void_p)
+    L.sf_route_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, pp]
+    L.sf_route_destroy.argtypes = [vp]
+    L.sf_route_destroy.restype = None
+    L.sf_route_set_stream.argtypes = [vp, vp]
+    L.sf_route_synchronize.argtypes = [vp]
+    L.sf_route_count.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    L.sf_route_agents_device.argtypes = [vp, C.c_int32, pp]
+    L.sf_route_gather.argtypes = [vp, C.POINTER(RouteSrc), C.POINTER(RouteDst)]
+    L.sf_route_scatter.argtypes = [vp, C.POINTER(RouteRows), C.POINTER(RouteRows)]
+    for n in ROUTE_EXPORTS:
+        if n != "sf_route_destroy":
+            getattr(L, n).restype = C.c_int
+    L._sf_route_bound = True
+
+
+def route_slots(assign, nets):
+    """The slot rule of sf_route_create on the host: (slot per agent, -1 for nobody's; per network the agents by slot)."""
+    assign = np.asarray(assign, dtype=np.int64).reshape(-1)
+    slot = np.full(len(assign), -1, dtype=np.int32)
+    agents_of = []
+    for k in range(int(nets)):
+        mine = np.flatnonzero(assign == k)
+        slot[mine] = np.arange(len(mine), dtype=np.int32)
+        agents_of.append(mine.astype(np.int32))
+    return slot, agents_of
+
+
+class Router:
+    """Agents of one environment batch routed to `nets` networks (`PolicyBatch` / `RewardBatch` / `RolloutBatch` objects of
+    count(k) agents each): assign[a] in [0, nets), or -1 for an agent no network plays.  Every commanded human of the
+    reference owns its network (bots/bot-0.5/Custom.hpp:161-165, bots/bot-1/Agent.hpp:84-101); this is that, for a batch.
+
+    Allocates, per network, the rows gather() fills — keys, vals [n][cap], counts [n], pov [n][160], reset [n] uint8 and,
+    with dense=True, dense [n][32][31][31] — and the compact rows the network answers into: cmd [n] uint8, action [n] int32,
+    probs [n][9], value, reward, disc [n] (attributes of `net[k]`).  One tick:
+
+        router.gather((keys, vals, counts, pov, cap), d_dense_ptr=..., reset_words=sim.done_view_device())
+        for k in range(nets): nets_[k].predict_sparse(**router.inputs(k), **router.outputs(k), seed=seed[k])
+        router.scatter({"cmd": d_cmd})
+
+    The draw of slot s is keyed by (seed, s, i): give every network its own seed."""
+
+    def __init__(self, assign, nets, cap=2048, dense=False, device=0):
+        import torch
+        import types
+        self.L = env.load_library()
+        _bind_route(self.L)
+        self.assign = np.ascontiguousarray(assign, dtype=np.int32).reshape(-1)
+        self.agents, self.nets, self.cap, self.device = len(self.assign), int(nets), int(cap), int(device)
+        self.h = None
+        h = C.c_void_p()
+        rc = self.L.sf_route_create(self.assign.ctypes.data_as(C.POINTER(C.c_int32)), self.agents, self.nets, self.device, C.byref(h))
+        if rc != 0:
+            raise env.StrikeForceError("sf_route_create failed (%d): %s" % (rc, self.L.sf_last_error().decode()))
+        self.h = h
+        dev = torch.device("cuda", self.device)
+        f32, i32, u8 = torch.float32, torch.int32, torch.uint8
+        self.net = []
+        for k in range(self.nets):
+            n = self.count(k)
+            new = lambda shape, dtype: torch.zeros((n,) + shape, dtype=dtype, device=dev)
+            self.net.append(types.SimpleNamespace(
+                keys=new((self.cap,), i32), vals=new((self.cap,), f32), counts=new((), i32), pov=new((HIDDEN,), f32),
+                dense=new((OBS_CHANNELS, OBS_WINDOW, OBS_WINDOW), f32) if dense else None, reset=new((), u8),
+                cmd=new((), u8), action=new((), i32), probs=new((ACTIONS,), f32), value=new((), f32), reward=new((), f32),
+                disc=new((), f32)))
+        self._torch, self._dev = torch, dev
+        ptr = lambda t: (t.data_ptr() or None) if t is not None else None
+        self._dst = (RouteDst * self.nets)(*[RouteDst(ptr(g.keys), ptr(g.vals), ptr(g.counts), ptr(g.pov), self.cap, ptr(g.dense),
+                                                      ptr(g.reset)) for g in self.net])
+        self._rows = (RouteRows * self.nets)(*[RouteRows(*[ptr(getattr(g, f)) for f in ROUTE_ROW_FIELDS]) for g in self.net])
+
+    def _ck(self, rc, what):
+        if rc != 0:
+            raise env.StrikeForceError("%s failed (%d): %s" % (what, rc, self.L.sf_last_error().decode()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.sf_route_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_stream(self, hip_stream):
+        self._ck(self.L.sf_route_set_stream(self.h, C.c_void_p(hip_stream)), "sf_route_set_stream")
+
+    def synchronize(self):
+        self._ck(self.L.sf_route_synchronize(self.h), "sf_route_synchronize")
+
+    def count(self, k):
+        n = C.c_int32()
+        self._ck(self.L.sf_route_count(self.h, int(k), C.byref(n)), "sf_route_count")
+        return n.value
+
+    def agents_of(self, k):
+        """Network k's agents by slot, as a device tensor view (int32 [count(k)], the library's memory: read it only)."""
+        p = C.c_void_p()
+        self._ck(self.L.sf_route_agents_device(self.h, int(k), C.byref(p)), "sf_route_agents_device")
+        n = self.count(k)
+        if n == 0:
+            return self._torch.zeros(0, dtype=self._torch.int32, device=self._dev)
+        iface = {"shape": (n,), "typestr": "<i4", "data": (p.value, False), "version": 2}
+        return self._torch.as_tensor(type("AgentsView", (), {"__cuda_array_interface__": iface})(), device=self._dev)
+
+    def gather(self, lists, d_dense_ptr=None, d_reset_mask_ptr=None, reset_words=None):
+        """lists: (d_keys_ptr, d_vals_ptr, d_counts_ptr, d_pov_ptr, cap) of ArenaBatch.observe_sparse_device, environment
+        order; cap must be this router's.  The other arguments as PolicyBatch.predict_sparse takes them.  One launch."""
+        s = RouteSrc()
+        s.d_keys, s.d_vals, s.d_counts, s.d_pov, s.cap = lists[0], lists[1], lists[2], lists[3], int(lists[4])
+        s.d_dense, s.d_reset_mask = d_dense_ptr, d_reset_mask_ptr
+        if reset_words is not None:
+            s.d_reset_words, s.reset_stride, s.reset_group = reset_words
+        self._ck(self.L.sf_route_gather(self.h, C.byref(s), self._dst), "sf_route_gather")
+
+    def inputs(self, k, record=False):
+        """Keyword arguments for network k: what PolicyBatch.predict_sparse and RewardBatch.reward_sparse take — or, with
+        record=True, RolloutBatch.record (which takes no dense rows)."""
+        g = self.net[k]
+        kw = dict(d_keys_ptr=g.keys.data_ptr(), d_vals_ptr=g.vals.data_ptr(), d_counts_ptr=g.counts.data_ptr(),
+                  d_pov_ptr=g.pov.data_ptr(), cap=self.cap, agents=self.count(k), d_reset_mask_ptr=g.reset.data_ptr())
+        if g.dense is not None and not record:
+            kw["d_dense_ptr"] = g.dense.data_ptr()
+        return kw
+
+    def outputs(self, k):
+        """Keyword arguments for PolicyBatch.predict_sparse's outputs of network k: its compact rows."""
+        g = self.net[k]
+        return dict(d_probs_ptr=g.probs.data_ptr(), d_value_ptr=g.value.data_ptr(), d_cmd_ptr=g.cmd.data_ptr(),
+                    d_action_ptr=g.action.data_ptr())
+
+    def scatter(self, env_rows):
+        """env_rows: {"cmd" | "action" | "probs" | "value" | "reward" | "disc": environment-order tensor or device address}; the
+        fields it names are copied from every network's compact rows to row a.  Rows of unassigned agents stay.  One launch."""
+        unknown = sorted(set(env_rows) - set(ROUTE_ROW_FIELDS))
+        if unknown:
+            raise ValueError("scatter: no such rows: %s" % unknown)
+        at = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        e = RouteRows(*[at(env_rows.get(f)) for f in ROUTE_ROW_FIELDS])
+        self._ck(self.L.sf_route_scatter(self.h, self._rows, C.byref(e)), "sf_route_scatter")
