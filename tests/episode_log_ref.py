@@ -22,6 +22,13 @@ class OracleEpisodes:
         A = self.cfg.arenas
         self.records = [[] for _ in range(A)]
         self.steps = np.zeros(A, dtype=np.int64)
+        self.over = np.zeros(A, dtype=bool)   # auto_reset == 0: the arena has ended its one game and stands still
+        self.first = np.zeros(A, dtype=np.int64)  # episodes counted when the log came on: earlier ones are not offered
+
+    def log_on(self):
+        """sf_episode_log(depth > 0) now: only games that end from here on are offered; their numbers go on counting."""
+        self.first = self.ended().astype(np.int64)
+        return self.first.copy()
 
     def _after_step(self):
         self.steps += 1
@@ -32,6 +39,8 @@ class OracleEpisodes:
         stride = seed_stride(self.cfg)
         for a in np.nonzero(done)[0]:
             assert done[a] == 1  # one loop iteration ends at most one episode
+            if self.over[a]:
+                continue  # (auto_reset == 0: sfo_done stays 1 after the end; there is no further episode)
             ep = len(self.records[a])
             tb = (self.tb0[a] + ep * stride) % (1 << 64)
             hdr = [a, ep, tb & 0xffffffff, tb >> 32, self.sr[a] & 0xffffffff, self.sr[a] >> 32, self.steps[a],
@@ -41,7 +50,7 @@ class OracleEpisodes:
             self.records[a].append(rec)
             self.steps[a] = 0
             if not self.cfg.auto_reset:
-                self.steps[a] = -(1 << 40)  # (the arena stands still: no further episode)
+                self.over[a] = True
 
     def step(self, cmd):
         self.sim.step(cmd)
@@ -55,19 +64,22 @@ class OracleEpisodes:
     def ended(self):
         return np.array([len(r) for r in self.records])
 
-    def ring(self, depth):
-        """The raw rings as they must be: [arenas][depth][record words], episode e in slot e & (depth - 1), -1 where empty."""
+    def ring(self, depth, upto=None):
+        """The raw rings as they must be: [arenas][depth][record words], episode e in slot e & (depth - 1), -1 where empty.
+        Episodes before log_on() are not in them; upto[a] (an earlier ended()) gives the rings as they were then."""
         rw = env.episode_record_words(self.cfg.n_agents)
         out = np.full((self.cfg.arenas, depth, rw), -1, dtype=np.int32)
         for a, recs in enumerate(self.records):
-            for e, r in enumerate(recs):
-                out[a, e & (depth - 1)] = r
+            n = len(recs) if upto is None else int(upto[a])
+            for e in range(max(int(self.first[a]), n - depth), n):
+                out[a, e & (depth - 1)] = recs[e]
         return out
 
-    def since(self, counts):
-        """Records of arena-ascending, episode-ascending order, each arena from its episode counts[a] on."""
+    def since(self, counts, upto=None):
+        """Records of arena-ascending, episode-ascending order, each arena from its episode counts[a] on (up to upto[a])."""
         rw = env.episode_record_words(self.cfg.n_agents)
-        rows = [r for a, recs in enumerate(self.records) for r in recs[counts[a]:]]
+        rows = [r for a, recs in enumerate(self.records)
+                for r in recs[int(counts[a]):(None if upto is None else int(upto[a]))]]
         return np.array(rows, dtype=np.int32).reshape(-1, rw)
 
 

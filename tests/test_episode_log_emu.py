@@ -1,9 +1,15 @@
 """The episode log's k_step part (sf_core.hpp latch_results<true>, the code of the k_step instance launched while the log
 is on) on the CPU wave emulator: the device core runs in K = 100 step launches with the log on, and after every launch its
 raw rings must equal what the oracle, stepped one step at a time, says: each finished episode's sfo_results behind its
-header, episode e in slot e & (depth - 1).  The shim (tests/episode_log/sf_emu_episodes.cpp) is tests/emu's build plus
-sf_episode_log / sf_episode_ring.  k_ep_late (the split step's records, the rings emptied by sf_reset on the device) has
-no emulator counterpart: tests/test_gpu_episode_log.py covers it."""
+header, episode e in slot e & (depth - 1).
+
+One-agent records on C3 and C2.  Records of 6 and of 16 agents on two cases of tests/episode_log_cases.py, whose quit
+schedule ends up to 13 games per arena and launch of 40 steps; and the first launch of every variant world, with the
+instance the host picks for it.
+
+The shim (tests/episode_log/sf_emu_episodes.cpp) is tests/emu's build plus sf_episode_log / sf_episode_ring.  k_ep_late
+(the split step's records, the rings emptied by sf_reset on the device) has no emulator counterpart:
+tests/test_gpu_episode_log.py and tests/test_gpu_episode_log_edges.py cover it."""
 import ctypes as C
 import os
 import subprocess
@@ -12,6 +18,8 @@ import numpy as np
 import pytest
 
 import emu_lib
+import episode_log_cases as ec
+import variant_cases as vc
 from episode_log_ref import OracleEpisodes
 from oracle_lib import Oracle
 from strikeforce_amd import abi, config, env
@@ -31,6 +39,7 @@ def shim(tmp_path_factory):
     abi.bind(L, "sfe_")
     L.sfe_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
     L.sfe_last_error.restype = C.c_char_p
+    L.sfe_last_variant.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
     L.sfe_episode_log.argtypes = [C.c_void_p, C.c_int32]
     L.sfe_episode_ring.argtypes = [C.c_void_p, C.c_void_p]
     return L
@@ -96,6 +105,50 @@ def test_emulated_rings_equal_the_oracle_after_every_launch(shim, which, arenas,
     for s in range(100):
         o2.step(cmds[s])
     assert (e.ring(depth) == o2.ring(depth)).all()
+    e.close()
+
+
+@pytest.mark.parametrize("case", ec.EMULATED, ids=lambda c: c.name)
+def test_emulated_rings_of_many_agents(shim, case):
+    """latch_results<true> under 6 agents (KITS: 56-word records) and under 16 (a variant_cases world: 136 words), five
+    arenas under the schedule of tests/episode_log_cases.py, depth 4 with arenas that end 13, 5, 4, 3, 1 and 0 games in a
+    launch of 40 steps; what the records carry is asserted in tests/test_episode_log_cases.py."""
+    run = ec.oracle_run(case)
+    w = case.workload()
+    e = EmuLog(w, shim)
+    assert e.episode_log(case.depth) == 0
+    e.reset(*case.seeds())
+    cmds = case.commands()
+    launches = case.launches()[:6]
+    for i, (s0, n) in enumerate(launches):
+        e.step_many(cmds[s0:s0 + n])
+        got, want = e.ring(case.depth), run.ring(i)
+        assert (got == want).all(), (i, np.argwhere(got != want)[:5])
+    assert e.last_variant("step") == vc.expected_variant(w.cfg)
+    per = run.per_launch()[:len(launches)]
+    assert per.max() > 3 * case.depth and {0, 1, case.depth - 1, case.depth, case.depth + 1} <= set(per.reshape(-1).tolist())
+    res = e.results()  # the newest record of every arena is what sf_results latched
+    for a in range(w.cfg.arenas):
+        n = int(run.ends[len(launches) - 1][a])
+        assert (run.o.records[a][n - 1][env.EPISODE_HDR_WORDS:] == res[a].reshape(-1)).all()
+    e.close()
+
+
+@pytest.mark.parametrize("case", ec.VARIANTS, ids=lambda c: c.name)
+def test_host_picks_the_expected_log_instance(shim, case):
+    """All 15 variant worlds at the 5 arenas and depth 4 the device tests run them with: with the log on the host launches
+    the instance variant_cases.expected_variant names (the emulated host's choice is the device host's: one dispatcher),
+    and the rings behind the first launch equal the oracle's."""
+    run = ec.oracle_run(case)
+    w = case.workload()
+    e = EmuLog(w, shim)
+    assert e.episode_log(case.depth) == 0
+    e.reset(*case.seeds())
+    s0, n = case.launches()[0]
+    e.step_many(case.commands()[s0:s0 + n])
+    assert e.last_variant("step") == vc.expected_variant(w.cfg)
+    got, want = e.ring(case.depth), run.ring(0)
+    assert (got == want).all(), np.argwhere(got != want)[:5]
     e.close()
 
 

@@ -4,6 +4,7 @@ tb = seeds()[a] + episode x stride)."""
 import numpy as np
 import pytest
 
+from episode_log_cases import lay_quits
 from episode_log_ref import OracleEpisodes, collect_like_kernel
 from oracle_lib import Oracle
 from strikeforce_amd import config, env
@@ -26,7 +27,7 @@ def device_cmds(cmds):
     return torch.from_numpy(np.ascontiguousarray(cmds)).cuda()
 
 
-def run_launches(which, arenas, steps, k, depth, stride=0, collect=True):
+def run_launches(which, arenas, steps, k, depth, stride=0, collect=True, quits=None):
     """Steps the GPU in k-step launches and the oracle one step at a time; after every launch the rings must equal the
     oracle's.  Returns (oracle log, GPU env, per-launch collections, ended counts before each launch)."""
     w = workload(which, arenas, stride)
@@ -36,6 +37,8 @@ def run_launches(which, arenas, steps, k, depth, stride=0, collect=True):
     g.reset(tb, sr)
     o = OracleEpisodes(Oracle(w), tb, sr)
     cmds, _ = config.bench_commands(arenas, w.cfg.n_agents, steps)
+    if quits:  # arena a's `ind` gives up every quits[a % len(quits)]-th step (0: never): episode_log_cases.lay_quits
+        lay_quits(cmds, [quits[a % len(quits)] for a in range(arenas)], ind=w.cfg.ind)
     d = device_cmds(cmds)
     got, before = [], []
     for s0 in range(0, steps, k):
@@ -191,11 +194,15 @@ def test_one_step_paths(path):
 
 @pytest.mark.parametrize("which,arenas,steps", [("C5", 64, 300), ("NATIVEGAME", 8, 300), ("C4", 64, 400)])
 def test_kernel_families(which, arenas, steps):
-    o, g, got, _ = run_launches(which, arenas, steps, 100, 8)
+    # random play alone ends 3 (C5) and 6 (C4) games in these runs: the quit schedule makes every configuration deliver
+    # records in every launch, at most 8 per arena and launch (nothing lost at depth 8), a quarter of the arenas as before
+    o, g, got, _ = run_launches(which, arenas, steps, 100, 8, quits=[15, 25, 50, 0])
     recs = np.concatenate([r for r, _ in got])
     assert all(c[1] == 0 for _, c in got)
+    assert all(c[0] >= arenas // 2 for _, c in got)  # every launch delivers records
     recs = recs[np.lexsort((recs[:, 1], recs[:, 0]))]  # (collections come launch by launch: arena-major within each)
     assert (recs == o.since([0] * arenas)).all()
+    assert len(recs) >= arenas * (steps // 100) and (o.ended()[np.arange(arenas) % 4 != 3] >= 2 * (steps // 100)).all()
     if which == "NATIVEGAME":
         assert o.ended().min() >= 2
     g.close()
