@@ -176,6 +176,40 @@ void sf_config_defaults(sf_config *cfg);
  * tb/serial: host arrays of `arenas` entries. */
 int sf_reset(sf_env *env, const uint64_t *tb, const uint64_t *serial);
 
+/* ---- restart of chosen arenas, on the device ------------------------------------------------------------------
+ * The reference starts each new game with a fresh setup() and a new `tb` (gameplay.hpp:1231-1277, :1233) whenever the
+ * player starts one, whatever any other game is doing.  sf_reset_arenas does that for the arenas a selection names and
+ * leaves every other arena alone: no word of any buffer of an arena that is not chosen is written.
+ * An arena is chosen if its mask flag is set, or (done_too) its game has ended (sf_arena_hdr.done == 1), or (max_steps >
+ * 0) its game is still running and has sf_arena_hdr.steps >= max_steps.  A chosen arena ends up as sf_reset with that
+ * (tb, serial) would have left it — setup() + load_data() + _srand + ++frame + the first loop top; done 0, sf_done 0;
+ * with auto_reset the warm-up of the episode after it armed at the new tb + reseed_stride — except that
+ *   - sf_arena_hdr.episodes keeps counting (it stays "episodes since the last whole sf_reset"), and
+ *   - the arena's result latch (sf_results), episode-log ring and log cursor are not touched: undelivered records survive.
+ * The game that was cut is abandoned: it is no episode, it is not logged and no counter moves.  A caller who wants the cut
+ * game's record ends it one tick earlier with the reference's own quit command '_' (gameplay.hpp:696, 874-877, 941-954;
+ * here the player's Hp drops to 0 and check_end ends the game, outcome SF_DIED): that game ends as an episode, is latched
+ * and logged, and done_too then restarts it.
+ * The restart is reported through d_selected, not through the done flags: a caller that lets sf_policy_predict_sparse read
+ * the flags in place (sf_done_view_device) must pass d_selected to sf_policy_reset_memory for arenas restarted this way.
+ * The call is one kernel launch in stream order on the environment's stream: no allocation, no copy, no host
+ * synchronisation; the struct travels in the kernel arguments (it may be a temporary).
+ * SF_ERR_STATE: before the first sf_reset, between sf_step_begin and sf_step_end, while a replay is loaded.  SF_ERR_ARG:
+ * exactly one of d_tb / d_serial NULL, mask_stride < 1 with a mask, max_steps < 0, or a non-NULL pointer that is not
+ * device memory of the environment's device, is not aligned (d_tb / d_serial: 8 bytes) or whose extent — d_mask:
+ * (arenas - 1) * mask_stride + 1 bytes, the others as below — reaches past its allocation; nothing is launched then. */
+typedef struct sf_reset_sel {
+  const uint8_t *d_mask;    /* device; arena a is chosen if d_mask[a * mask_stride] != 0.  NULL: nobody by mask */
+  int32_t mask_stride;      /* bytes between two arenas' flags: 1, or n_agents to pass sf_done_device's output as it is */
+  int32_t done_too;         /* != 0: also every arena whose game has ended (done == 1) */
+  int32_t max_steps;        /* > 0: also every arena whose running game has sf_arena_hdr.steps >= max_steps */
+  const uint64_t *d_tb;     /* device, [arenas]; entries of arenas not chosen are not read */
+  const uint64_t *d_serial; /* both NULL: the next seed by auto_reset's own rule, tb + reseed_stride, serial kept */
+  uint8_t *d_selected;      /* optional out, device, [arenas][n_agents]: 1 for every agent of a restarted arena, else 0 —
+                               the layout sf_policy_reset_memory and sf_rollout_record take */
+} sf_reset_sel;
+int sf_reset_arenas(sf_env *env, const sf_reset_sel *sel);
+
 /* One iteration of gameplay::play()'s while(true) body, gameplay.hpp:1452-1471, followed by the next
  * iteration's loop-top (spawns + check_end, gameplay.hpp:1444-1450), for every arena.
  * cmd: host array [arenas][n_agents] of reference command chars (valid_commands gameplay.hpp:45, plus

@@ -130,6 +130,14 @@ class PortalRec(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("active", "f", "r", "c")]
 
 
+class ResetSel(C.Structure):
+    """sf_reset_sel: which arenas sf_reset_arenas restarts, and on which seeds (device pointers as integers)."""
+    _fields_ = [
+        ("d_mask", C.c_void_p), ("mask_stride", C.c_int32), ("done_too", C.c_int32), ("max_steps", C.c_int32),
+        ("d_tb", C.c_void_p), ("d_serial", C.c_void_p), ("d_selected", C.c_void_p),
+    ]
+
+
 def struct_to_dict(s):
     out = {}
     for name, _ in s._fields_:

@@ -1,6 +1,6 @@
 // sf_api.hip — libstrikeforce_amd.so: the gfx950 runtime behind the C-ABI of include/strikeforce.h.
 //
-//   the thin __global__ wrappers around Core<..> (sf_core.hpp): k_reset, k_step, k_step_half <NB, HP, BM, ZL>, one wavefront
+//   the thin __global__ wrappers around Core<..> (sf_core.hpp): k_reset, k_reset_sel, k_step, k_step_half <NB, HP, BM, ZL>, one wavefront
 //     per arena (the instance a configuration runs: sf_types.hpp with_variant), k_step_fixed<Shape> (k_step with a listed
 //     configuration's fields as constants: sf_types.hpp FixedShapes), k_agent_alive, k_done, k_ep_late, k_replay_fetch
 //   k_rank (k_step's launch order) and the episode-log collection kernels k_ep_plan / k_ep_copy
@@ -41,6 +41,14 @@ template <int NB, bool HP, bool BM, bool ZL>
 __global__ __launch_bounds__(64) void k_reset(Params p, const uint64_t *tb, const uint64_t *serial) {
   extern __shared__ __attribute__((aligned(2048))) uint8_t lds[];  // the RNG power table comes first (W::pow_pair)
   Core<WaveGfx950, NB, HP, BM, ZL>::reset_body(lds, p, (int)blockIdx.x, tb, serial);
+}
+
+// sf_reset_arenas: k_reset for the arenas `sel` chooses (sf_core.hpp reset_sel_body), built for the variants k_reset is built
+// for.  One wavefront per arena; a wavefront whose arena is not chosen ends behind four loads and its bytes of sel.selected.
+template <int NB, bool HP, bool BM, bool ZL>
+__global__ __launch_bounds__(64) void k_reset_sel(Params p, ResetSel sel) {
+  extern __shared__ __attribute__((aligned(2048))) uint8_t lds[];  // the RNG power table comes first (W::pow_pair)
+  Core<WaveGfx950, NB, HP, BM, ZL>::reset_sel_body(lds, p, (int)blockIdx.x, sel);
 }
 
 // LOG: the instance launched while the episode log is on (sf_core.hpp latch_results<LOG>); with the log off the kernel is
@@ -281,6 +289,37 @@ struct HipRT {
   int launch_reset(const Params &p, int NB, const uint64_t *tb, const uint64_t *serial) {
     SF_HIP(hipSetDevice(device));
     return launch_arenas(p, NB, [](auto v) { return &k_reset<v.NB, v.HP, v.BM, v.ZL>; }, tb, serial);
+  }
+  // `bytes` bytes at q: device memory of this runtime's device, aligned, wholly inside its allocation (as
+  // sf_policy_load_weights checks its sources).  A host pointer is answered here and never reaches a kernel.
+  int check_device_range(const void *q, size_t bytes, size_t align, const char *name) const {
+    const std::string n = std::string("sf_reset_arenas: ") + name;
+    if (reinterpret_cast<uintptr_t>(q) & (align - 1)) return fail(SF_ERR_ARG, n + " is not " + std::to_string(align) + "-byte aligned");
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, q) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+      (void)hipGetLastError();  // (a host pointer is an error of the query: it is answered here, not left behind)
+      return fail(SF_ERR_ARG, n + " is not device memory of the environment's device");
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(q)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(SF_ERR_ARG, n + ": its allocation is unknown to the runtime");
+    }
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(base), addr = reinterpret_cast<uintptr_t>(q);
+    if (addr < lo || addr - lo > size || bytes > size - (addr - lo)) return fail(SF_ERR_ARG, n + " reaches past the end of its allocation");
+    return SF_OK;
+  }
+  // one launch, the struct in the kernel arguments; nothing is allocated, copied or waited for
+  int launch_reset_sel(const Params &p, int NB, const ResetSel &sel) {
+    SF_HIP(hipSetDevice(device));
+    const size_t A = (size_t)p.A;
+    int rc;
+    if (sel.mask && (rc = check_device_range(sel.mask, (A - 1) * (size_t)sel.mask_stride + 1, 1, "d_mask"))) return rc;
+    if (sel.tb && (rc = check_device_range(sel.tb, A * sizeof(uint64_t), 8, "d_tb"))) return rc;
+    if (sel.serial && (rc = check_device_range(sel.serial, A * sizeof(uint64_t), 8, "d_serial"))) return rc;
+    if (sel.selected && (rc = check_device_range(sel.selected, A * (size_t)p.n_agents, 1, "d_selected"))) return rc;
+    return launch_arenas(p, NB, [](auto v) { return &k_reset_sel<v.NB, v.HP, v.BM, v.ZL>; }, sel);
   }
   bool can_rank() const { return true; }
   // k_rank runs right in front of the k_step launch it orders, inside that launch's pair of timing events: what
@@ -556,6 +595,10 @@ int sf_destroy(sf_env *env) {
 int sf_reset(sf_env *env, const uint64_t *tb, const uint64_t *serial) {
   SF_ENV(env);
   return env->e.reset(tb, serial);
+}
+int sf_reset_arenas(sf_env *env, const sf_reset_sel *sel) {
+  SF_ENV(env);
+  return env->e.reset_arenas(sel);
 }
 int sf_step(sf_env *env, const uint8_t *cmd) {
   SF_ENV(env);

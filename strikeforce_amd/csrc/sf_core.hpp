@@ -2234,6 +2234,43 @@ struct Core {
     store(S, lds, p, a);
   }
 
+  // sf_reset_arenas: reset_body for the arenas `r` chooses, every other arena left as it is.  The verdict comes first and
+  // is wave-uniform: the mask byte, SC_DONE, SC_STEPS and SC_EPISODES are loaded unconditionally (an absent mask reads the
+  // arena's own scalar block instead, an address that is always valid) and every lane gets lane 0's copy.  A wave that is
+  // not chosen writes its zeros of r.selected and ends before any table is staged: it writes nothing else.  A chosen wave
+  // runs reset_body's sequence with the arena's (tb, serial) — r.tb / r.serial, or auto_reset's own rule, the running
+  // seed + reseed with the serial kept — and keeps the arena's episode count; the result latch, the episode-log ring and
+  // its cursor are not its business, and a first loop top that ends the new game at once latches as k_reset's does.
+  static SF_DEV void reset_sel_body(uint8_t *lds, const Params &p, int a, const ResetSel &r) {
+    const int32_t *const sc = p.scal + (size_t)a * SC_WORDS;
+    const uint8_t *const mp = r.mask ? r.mask + (size_t)a * (size_t)r.mask_stride : reinterpret_cast<const uint8_t *>(sc);
+    const uint32_t mb = W::readlane(W::gload_u8(mp, V(0u), W::all()), 0u);
+    const int32_t done = W::uload_i32(sc + SC_DONE), steps = W::uload_i32(sc + SC_STEPS);
+    const int32_t episodes = W::uload_i32(sc + SC_EPISODES);
+    const bool chosen = (r.mask && mb != 0u) || (r.done_too && done != 0) || (r.max_steps > 0 && done == 0 && steps >= r.max_steps);
+    if (r.selected)
+      W::gstore_u8(r.selected + (size_t)a * (size_t)SF_SHAPE(n_agents), W::lane(), V(chosen ? 1u : 0u),
+                   W::ltu(W::lane(), (uint32_t)SF_SHAPE(n_agents)));
+    if (!chosen) return;
+    uint64_t tb, serial;
+    if (r.tb) {
+      tb = r.tb[a], serial = r.serial[a];
+    } else {
+      tb = (((uint64_t)(uint32_t)W::uload_i32(sc + SC_TB_HI) << 32) | (uint32_t)W::uload_i32(sc + SC_TB_LO)) + (uint64_t)(uint32_t)p.reseed;
+      serial = ((uint64_t)(uint32_t)W::uload_i32(sc + SC_SR_HI) << 32) | (uint32_t)W::uload_i32(sc + SC_SR_LO);
+    }
+    Arena S;
+    S.episodes = episodes, S.ended = 0;
+    S.pd01 = S.pd23 = S.pd45 = 0u;
+    lds = tables(S, lds, p, a);
+    S.rl2 = V(RL_ZERO), S.rseed2 = V(0u), S.warm = 0u, S.wrate = 1u;
+    if constexpr (ZL) S.zwhi = (uint32_t)zw_for(SF_SHAPE(Z)), S.pwhi = (uint32_t)zw_for(p.P);  // the whole tables are written, as by reset_body: the game before may have had higher words in use
+    reset_state(S, lds, p, tb, serial, false);
+    ++S.frame;  // G:1441
+    loop_top(S, lds, p, a);
+    store(S, lds, p, a);
+  }
+
   // cmds: [k][A][n_agents].  The gfx950 kernels call step_body_t<LOG> with the instance the host picked; step_body picks
   // it from Tables at run time, for a runtime that has one code path (the wave emulator of tests/emu)
   static SF_DEV void step_body(uint8_t *lds, const Params &p, int a, const uint8_t *cmds, int k) {

@@ -208,6 +208,14 @@ struct has_fixed_shapes : std::false_type {};
 template <class R>
 struct has_fixed_shapes<R, decltype((void)std::declval<R &>().fixed_shape)> : std::true_type {};
 
+// whether a runtime has k_reset_sel (sf_reset_arenas).  The HIP runtime has it; the emulator's runtime of tests/emu does
+// not (tests/reset_sel_emu supplies one that has), and Env::reset_arenas answers SF_ERR_STATE there
+template <class R, class = void>
+struct has_reset_sel : std::false_type {};
+template <class R>
+struct has_reset_sel<R, decltype((void)std::declval<R &>().launch_reset_sel(std::declval<const Params &>(), 1, std::declval<const ResetSel &>()))>
+    : std::true_type {};
+
 template <class RT>
 struct Env {
   sf_config cfg;
@@ -416,6 +424,26 @@ struct Env {
     mid_step = false;
     steps_since_rank = 1 << 30;
     return rt.sync();
+  }
+
+  // sf_reset_arenas: one stream-ordered launch that restarts the chosen arenas (sf_core.hpp reset_sel_body).  Nothing is
+  // allocated, copied or waited for; the result latch, the episode-log rings and their cursors are left alone
+  int reset_arenas(const sf_reset_sel *sel) {
+    if (!sel) return fail(SF_ERR_ARG, "sf_reset_arenas: null sf_reset_sel");
+    if (!was_reset) return fail(SF_ERR_STATE, "sf_reset_arenas before sf_reset");
+    if (int rc = not_mid_step("sf_reset_arenas")) return rc;
+    if (rp.status) return fail(SF_ERR_STATE, "sf_reset_arenas while a replay is loaded (sf_replay_load)");
+    if (!sel->d_tb != !sel->d_serial) return fail(SF_ERR_ARG, "sf_reset_arenas: d_tb and d_serial must both be given or both be NULL");
+    if (sel->d_mask && sel->mask_stride < 1) return fail(SF_ERR_ARG, "sf_reset_arenas: mask_stride must be at least 1");
+    if (sel->max_steps < 0) return fail(SF_ERR_ARG, "sf_reset_arenas: max_steps must not be negative");
+    if constexpr (has_reset_sel<RT>::value) {
+      const ResetSel r = {sel->d_mask, sel->d_mask ? sel->mask_stride : 0, sel->done_too, sel->max_steps, sel->d_tb, sel->d_serial, sel->d_selected};
+      if (int rc = rt.launch_reset_sel(p, NB, r)) return rc;
+      steps_since_rank = 1 << 30;  // the populations the launch order was built from are gone
+      return SF_OK;
+    } else {
+      return fail(SF_ERR_STATE, "sf_reset_arenas: this runtime has no k_reset_sel");
+    }
   }
 
   int step_host(const uint8_t *cmd) {

@@ -128,6 +128,19 @@ struct Replay {
   uint8_t *taken;          // [A][n_agents]: the line each commanded human took in the last iteration, 0 where none
 };
 
+// ---- restart of chosen arenas (sf_reset_arenas, sf_core.hpp reset_sel_body) ---------------------------------------
+// sf_reset_sel of strikeforce.h as k_reset_sel takes it, by value in the kernel arguments.  A struct of its own, like
+// Replay: Params stays as it is.
+struct ResetSel {
+  const uint8_t *mask;     // arena a is chosen if mask[a * mask_stride] != 0; null: nobody by mask
+  int32_t mask_stride;
+  int32_t done_too;        // != 0: also every arena with SC_DONE set
+  int32_t max_steps;       // > 0: also every running arena with SC_STEPS >= max_steps
+  const uint64_t *tb;      // [A], read for chosen arenas only; both null: tb + reseed, serial kept
+  const uint64_t *serial;
+  uint8_t *selected;       // null, or [A][n_agents]: 1 for every agent of a restarted arena, else 0
+};
+
 // ---- everything a kernel needs -----------------------------------------------------------------------
 struct Params {
   int32_t A, F, N, M, cells, cells_pad;

@@ -69,6 +69,9 @@ def load_library():
             L.sf_replay_commands_device.argtypes = [vp, vp]
             for n in REPLAY_EXPORTS:
                 getattr(L, n).restype = C.c_int
+        if hasattr(L, "sf_reset_arenas"):  # (restart of chosen arenas; an older build loaded through SF_LIBRARY_PATH lacks it)
+            L.sf_reset_arenas.argtypes = [vp, C.POINTER(abi.ResetSel)]
+            L.sf_reset_arenas.restype = C.c_int
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -105,7 +108,8 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_comm_unique_id", "sf_comm_init", "sf_results_allgather", "sf_comm_wait", "sf_comm_ranks",
            "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
-           "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device"]
+           "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device",
+           "sf_reset_arenas"]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -171,6 +175,19 @@ class ArenaBatch:
 
     def reset(self, tb, serial):
         self._ck(self.L.sf_reset(self.h, tb, serial), "sf_reset")
+
+    def reset_arenas(self, mask_ptr=None, mask_stride=1, done=False, max_steps=0, tb_ptr=None, serial_ptr=None,
+                     selected_ptr=None):
+        """Restart the chosen arenas on the device, in stream order, every other arena untouched (sf_reset_arenas): those
+        whose byte at mask_ptr[a * mask_stride] is set, with done=True those whose game has ended, with max_steps > 0
+        those whose running game has played that many steps.  tb_ptr / serial_ptr: device uint64 [arenas], read for the
+        chosen arenas only; both None: tb + reseed_stride, the serial kept.  selected_ptr: device uint8
+        [arenas][n_agents], 1 for every agent of a restarted arena — what PolicyBatch.reset_memory and the rollout
+        buffer's restart mask take.  All pointers are device addresses."""
+        if not hasattr(self.L, "sf_reset_arenas"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_reset_arenas")
+        sel = abi.ResetSel(mask_ptr, int(mask_stride), 1 if done else 0, int(max_steps), tb_ptr, serial_ptr, selected_ptr)
+        self._ck(self.L.sf_reset_arenas(self.h, C.byref(sel)), "sf_reset_arenas")
 
     def step(self, cmd):
         cmd = np.ascontiguousarray(cmd, dtype=np.uint8)
