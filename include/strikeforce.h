@@ -210,6 +210,51 @@ typedef struct sf_reset_sel {
 } sf_reset_sel;
 int sf_reset_arenas(sf_env *env, const sf_reset_sel *sel);
 
+/* ---- save, restore and fork arenas mid-game, on the device ------------------------------------------------------
+ * The reference can return to an earlier moment of a game in one way only: replaying its logged commands from tick 0
+ * (gameplay.hpp:968-986; here sf_replay_*).  A snapshot keeps `slots` arena states in device memory of its own; save copies
+ * arenas into slots, load copies slots into arenas, and many arenas may load one slot: that is the fork.
+ * A slot carries the arena's rows of the human, zombie, bullet and exit tables, both generators (the running one and the
+ * next episode's being warmed under auto_reset), the whole scalar block (frame, counters, seeds, done / ended flags, the
+ * phase draws), the cell flags and the two per-cell side tables: everything sf_state_digest, sf_dump_arena, sf_phase_draws,
+ * sf_done* and the next step read.  A slot does NOT carry, and a load does not touch:
+ *   - sf_arena_hdr.episodes of the destination, which keeps counting as after sf_reset_arenas;
+ *   - the result latch (sf_results);
+ *   - the episode-log ring and its cursor: undelivered records survive and the log's ordinals stay monotonic;
+ *   - the cursors of a loaded replay, rollout buffers, and the memory of any network (sf_policy_memory_rows moves that).
+ * Every other scalar comes from the slot as it is, the done / ended flags and the seed included: a save taken between a step
+ * and the next predict resumes with the same restart flags, and a loaded arena's later auto_reset restarts follow the
+ * SOURCE's seed sequence.  Forks are therefore twins until their commands differ, and the episode log's "tb is unique
+ * across shards" no longer holds for them: tell forks apart by arena, not by seed.
+ * d_slot_of_arena: device int32 [arenas].  -1: the arena takes no part — no word of it is written (load), and no word of
+ * a slot nobody names is written (save).  An index outside [-1, slots), and a load from a slot that was never saved or
+ * imported, are skipped with the state left as it was and counted (sf_snapshot_status); such an index never becomes an
+ * address.  Two arenas saving into one slot in one call is a caller error whose only guarantee is memory safety.
+ * Save and load are one kernel launch each, in stream order on the environment's stream: no allocation, no copy, no host
+ * synchronisation.  create, destroy, status, export and import synchronise.  Destroy a snapshot before its environment.
+ * SF_ERR_STATE: before the first sf_reset, between sf_step_begin and sf_step_end, while a replay is loaded, a snapshot used
+ * with an environment other than the one it was created for, an export of an empty slot.  SF_ERR_ARG: null handles,
+ * slots < 1, a slot out of range (export / import), a d_slot_of_arena that is not device memory of the environment's
+ * device, is not 4-byte aligned or is shorter than `arenas` entries; nothing is launched then.
+ * A blob (export / import, the checkpoint path) is a 24-byte header — magic, layout version, payload length, a 64-bit
+ * fingerprint of the configuration — and the slot's bytes.  The fingerprint covers every sf_config field that shapes or
+ * interprets the state (dimensions, caps, mode, level, n_agents, ind, teams, auto_reset, the effective reseed stride,
+ * timer_frames_per_level, map and portal table, profiles, items) and leaves out `arenas` and `device`: a blob may go into
+ * an environment with another arena count (set reseed_stride explicitly then: its default is the arena count).
+ * sf_snapshot_import refuses a blob that is too short or has another magic, version, length or fingerprint with
+ * SF_ERR_ARG and touches nothing. */
+typedef struct sf_snapshot sf_snapshot;       /* opaque; device memory for `slots` arena states of env's configuration */
+int sf_snapshot_create(sf_env *env, int32_t slots, sf_snapshot **out);
+int sf_snapshot_destroy(sf_snapshot *s);
+int sf_snapshot_slot_bytes(sf_env *env, int64_t *device_bytes, int64_t *blob_bytes);   /* to budget before create */
+/* arena a -> slot d_slot_of_arena[a]; -1: arena not saved.  Device int32 [arenas]. */
+int sf_snapshot_save(sf_env *env, sf_snapshot *s, const int32_t *d_slot_of_arena);
+/* arena a <- slot d_slot_of_arena[a]; -1: arena untouched.  Many arenas may name one slot: that is the fork. */
+int sf_snapshot_load(sf_env *env, sf_snapshot *s, const int32_t *d_slot_of_arena);
+int sf_snapshot_status(sf_snapshot *s, int32_t out_host[4]);   /* skipped: empty slot, index out of range, 0, 0; clears */
+int sf_snapshot_export(sf_snapshot *s, int32_t slot, void *blob_host, int64_t bytes);        /* one slot -> host blob */
+int sf_snapshot_import(sf_snapshot *s, int32_t slot, const void *blob_host, int64_t bytes);  /* host blob -> one slot */
+
 /* One iteration of gameplay::play()'s while(true) body, gameplay.hpp:1452-1471, followed by the next
  * iteration's loop-top (spawns + check_end, gameplay.hpp:1444-1450), for every arena.
  * cmd: host array [arenas][n_agents] of reference command chars (valid_commands gameplay.hpp:45, plus

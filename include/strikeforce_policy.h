@@ -200,6 +200,17 @@ int sf_reward_sparse(sf_policy *r, const sf_reward_io *io, int32_t agents);
 int sf_policy_get_memory(sf_policy *p, int32_t agent, float *h, float *action_input);
 int sf_policy_set_memory(sf_policy *p, int32_t agent, const float *h, const float *action_input);
 
+/* The same for many agents in one launch, storage the caller's: the network memory that goes with a saved or forked arena
+ * (strikeforce.h sf_snapshot_save / sf_snapshot_load), for policy and reward objects alike.  Agents [0, agents) are looked
+ * at.  Many agents may name one row when reading rows (the fork); two agents writing one row is a caller error whose only
+ * guarantee is memory safety.  A row index outside [-1, rows) is skipped like -1 and never dereferenced.  One launch in
+ * stream order on the object's stream: no allocation, no copy, no host synchronisation.  SF_ERR_ARG: a null object or
+ * buffer, agents outside [1, max_agents], rows < 1, or a buffer that is not device memory of the object's device, is not
+ * 4-byte aligned or is shorter than stated (the checks sf_policy_load_weights makes); nothing is launched then. */
+/* to_rows != 0: agent g's h[2][160] and action one-hot[9] -> row d_row_of_agent[g];  0: row -> agent.  -1: agent skipped. */
+int sf_policy_memory_rows(sf_policy *p, int32_t to_rows, float *d_h /*[rows][2][160]*/, float *d_action /*[rows][9]*/,
+                          const int32_t *d_row_of_agent, int32_t rows, int32_t agents);
+
 int sf_policy_set_stream(sf_policy *p, void *hip_stream);
 int sf_policy_synchronize(sf_policy *p);
 

@@ -138,6 +138,31 @@ class ResetSel(C.Structure):
     ]
 
 
+SNAPSHOT_BLOB_HEADER = 24  # bytes in front of a slot's bytes in a blob: magic, layout version, payload length, fingerprint
+SNAPSHOT_BLOB_MAGIC = 0x4E534653  # "SFSN", little-endian
+SNAPSHOT_BLOB_VERSION = 1
+SNAPSHOT_STATUS_WORDS = 4  # sf_snapshot_status: arenas skipped for an empty slot, for an index out of range, 0, 0
+SNAPSHOT_EXPORTS = ("snapshot_create", "snapshot_destroy", "snapshot_slot_bytes", "snapshot_save", "snapshot_load",
+                    "snapshot_status", "snapshot_export", "snapshot_import")
+
+
+def bind_snapshot(lib, prefix):
+    """Declare the sf_snapshot_* entry points (strikeforce.h) on a loaded library; handles and pointers as integers."""
+    g = lambda n: getattr(lib, prefix + n)
+    vp = C.c_void_p
+    g("snapshot_create").argtypes = [vp, C.c_int32, C.POINTER(vp)]
+    g("snapshot_destroy").argtypes = [vp]
+    g("snapshot_slot_bytes").argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    g("snapshot_save").argtypes = [vp, vp, vp]
+    g("snapshot_load").argtypes = [vp, vp, vp]
+    g("snapshot_status").argtypes = [vp, C.POINTER(C.c_int32 * SNAPSHOT_STATUS_WORDS)]
+    g("snapshot_export").argtypes = [vp, C.c_int32, vp, C.c_int64]
+    g("snapshot_import").argtypes = [vp, C.c_int32, vp, C.c_int64]
+    for n in SNAPSHOT_EXPORTS:
+        g(n).restype = C.c_int
+    return lib
+
+
 def struct_to_dict(s):
     out = {}
     for name, _ in s._fields_:

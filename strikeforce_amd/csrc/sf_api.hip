@@ -4,6 +4,7 @@
 //     per arena (the instance a configuration runs: sf_types.hpp with_variant), k_step_fixed<Shape> (k_step with a listed
 //     configuration's fields as constants: sf_types.hpp FixedShapes), k_agent_alive, k_done, k_ep_late, k_replay_fetch
 //   k_rank (k_step's launch order) and the episode-log collection kernels k_ep_plan / k_ep_copy
+//   k_snapshot<SAVE>, the copy between the state buffers and a snapshot object (sf_snapshot.hpp)
 //   HipRT, the runtime Env<RT> (sf_host.hpp) launches through
 //   Comm, the RCCL exchange of the multi-GPU path
 //   the extern "C" entry points
@@ -24,6 +25,7 @@
 #include "sf_core.hpp"
 #include "sf_obs.hpp"
 #include "sf_obs_kernels.hpp"
+#include "sf_snapshot.hpp"
 #include "sf_host.hpp"
 // clang-format on
 
@@ -229,6 +231,32 @@ __global__ __launch_bounds__(256) void k_ep_copy(const uint32_t *ring, int A, in
   }
 }
 
+
+// sf_snapshot_save / sf_snapshot_load (sf_snapshot.hpp): what the copy body needs beyond the core's backend — 16 bytes per
+// lane at a byte offset from a wave-uniform base, 16-bit stores, and the count of a skipped arena.  Nothing here is used
+// by any other kernel.
+struct SnapGfx950 : WaveGfx950 {
+  using V4 = u32x4;
+  static SF_DEV V4 gload16(const uint8_t *base, V byte_off, P pred) {
+    return pred ? *reinterpret_cast<const SF_GLOBAL u32x4 *>(gptr(base) + byte_off) : (u32x4)(0u);
+  }
+  static SF_DEV void gstore16(uint8_t *base, V byte_off, V4 val, P pred) {
+    if (pred) *reinterpret_cast<SF_GLOBAL u32x4 *>(gptr(base) + byte_off) = val;
+  }
+  static SF_DEV void gstore_u16(uint16_t *base, V idx, V val, P pred) {
+    if (pred) gptr(base)[idx] = (uint16_t)val;
+  }
+  static SF_DEV void ucount(uint32_t *counter) {  // one vector atomic per skipped arena: the rare path
+    if (lane() == 0u) (void)__hip_atomic_fetch_add(gptr(counter), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+};
+// One instance per direction for every configuration: the sizes travel in the piece table.  Grid (arenas, parts), one
+// wavefront per workgroup (WaveGfx950::lane() is threadIdx.x).
+template <bool SAVE>
+__global__ __launch_bounds__(64) void k_snapshot(Snap s) {
+  SnapCore<SnapGfx950, SAVE>::body(s, (int)blockIdx.x, (int)blockIdx.y);
+}
+
 #define SF_HIP(call)                                                                       \
   do {                                                                                     \
     hipError_t e_ = (call);                                                                \
@@ -292,8 +320,8 @@ struct HipRT {
   }
   // `bytes` bytes at q: device memory of this runtime's device, aligned, wholly inside its allocation (as
   // sf_policy_load_weights checks its sources).  A host pointer is answered here and never reaches a kernel.
-  int check_device_range(const void *q, size_t bytes, size_t align, const char *name) const {
-    const std::string n = std::string("sf_reset_arenas: ") + name;
+  int check_device_range(const void *q, size_t bytes, size_t align, const char *name, const char *who = "sf_reset_arenas") const {
+    const std::string n = std::string(who) + ": " + name;
     if (reinterpret_cast<uintptr_t>(q) & (align - 1)) return fail(SF_ERR_ARG, n + " is not " + std::to_string(align) + "-byte aligned");
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, q) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
@@ -320,6 +348,14 @@ struct HipRT {
     if (sel.serial && (rc = check_device_range(sel.serial, A * sizeof(uint64_t), 8, "d_serial"))) return rc;
     if (sel.selected && (rc = check_device_range(sel.selected, A * (size_t)p.n_agents, 1, "d_selected"))) return rc;
     return launch_arenas(p, NB, [](auto v) { return &k_reset_sel<v.NB, v.HP, v.BM, v.ZL>; }, sel);
+  }
+  // sf_snapshot_save / sf_snapshot_load: one launch, the piece table in the kernel arguments
+  int launch_snapshot(const Snap &k, int parts, bool save) {
+    SF_HIP(hipSetDevice(device));
+    if (int rc = check_device_range(k.slot_of_arena, (size_t)k.A * sizeof(int32_t), 4, "d_slot_of_arena", save ? "sf_snapshot_save" : "sf_snapshot_load"))
+      return rc;
+    const dim3 grid((unsigned)k.A, (unsigned)parts);
+    return save ? launch(k_snapshot<true>, grid, dim3(64), 0, k) : launch(k_snapshot<false>, grid, dim3(64), 0, k);
   }
   bool can_rank() const { return true; }
   // k_rank runs right in front of the k_step launch it orders, inside that launch's pair of timing events: what
@@ -557,6 +593,9 @@ struct sf_env {
   sf::Env<sf::HipRT> e;
   sf::Comm comm;
 };
+struct sf_snapshot {
+  sf::Env<sf::HipRT>::Snapshot *s;
+};
 
 using sf::fail;  // SF_HIP in the entry points below
 
@@ -599,6 +638,51 @@ int sf_reset(sf_env *env, const uint64_t *tb, const uint64_t *serial) {
 int sf_reset_arenas(sf_env *env, const sf_reset_sel *sel) {
   SF_ENV(env);
   return env->e.reset_arenas(sel);
+}
+int sf_snapshot_create(sf_env *env, int32_t slots, sf_snapshot **out) {
+  if (!out) return sf::fail(SF_ERR_ARG, "sf_snapshot_create: null output handle");
+  *out = nullptr;
+  SF_ENV(env);
+  sf_snapshot *h = new (std::nothrow) sf_snapshot{nullptr};
+  if (!h) return sf::fail(SF_ERR_MEMORY, "host allocation failed");
+  if (int rc = env->e.snapshot_create(slots, &h->s)) {
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return SF_OK;
+}
+int sf_snapshot_destroy(sf_snapshot *s) {
+  if (!s) return SF_OK;
+  const int rc = s->s->owner->snapshot_destroy(s->s);
+  delete s;
+  return rc;
+}
+int sf_snapshot_slot_bytes(sf_env *env, int64_t *device_bytes, int64_t *blob_bytes) {
+  SF_ENV(env);
+  return env->e.snapshot_slot_bytes(device_bytes, blob_bytes);
+}
+int sf_snapshot_save(sf_env *env, sf_snapshot *s, const int32_t *d_slot_of_arena) {
+  SF_ENV(env);
+  return env->e.snapshot_copy(s ? s->s : nullptr, d_slot_of_arena, true);
+}
+int sf_snapshot_load(sf_env *env, sf_snapshot *s, const int32_t *d_slot_of_arena) {
+  SF_ENV(env);
+  return env->e.snapshot_copy(s ? s->s : nullptr, d_slot_of_arena, false);
+}
+#define SF_SNAP(s) \
+  if (!(s)) return sf::fail(SF_ERR_ARG, "null snapshot")
+int sf_snapshot_status(sf_snapshot *s, int32_t out_host[4]) {
+  SF_SNAP(s);
+  return s->s->owner->snapshot_status(s->s, out_host);
+}
+int sf_snapshot_export(sf_snapshot *s, int32_t slot, void *blob_host, int64_t bytes) {
+  SF_SNAP(s);
+  return s->s->owner->snapshot_export(s->s, slot, blob_host, bytes);
+}
+int sf_snapshot_import(sf_snapshot *s, int32_t slot, const void *blob_host, int64_t bytes) {
+  SF_SNAP(s);
+  return s->s->owner->snapshot_import(s->s, slot, blob_host, bytes);
 }
 int sf_step(sf_env *env, const uint8_t *cmd) {
   SF_ENV(env);

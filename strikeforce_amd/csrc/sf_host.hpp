@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <new>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -18,6 +19,7 @@
 #include "../../include/strikeforce.h"
 #include "sf_types.hpp"
 #include "sf_obs.hpp"
+#include "sf_snapshot_blob.hpp"
 
 namespace sf {
 
@@ -780,6 +782,162 @@ struct Env {
     if (!d_words || !stride || !group) return fail(SF_ERR_ARG, "null argument");
     *d_words = p.scal + (p.auto_reset ? SC_ENDED : SC_DONE), *stride = SC_WORDS, *group = p.n_agents;
     return SF_OK;
+  }
+
+  // ---- arena snapshots (sf_snapshot_*; the copy is sf_snapshot.hpp snapshot body, k_snapshot) ------------------------
+  // row length and the environment's base of every piece of sf_types.hpp Snap, in the blob's order
+  void snap_rows(uint32_t row[SNAP_PIECES], uint8_t *base[SNAP_PIECES]) const {
+    const size_t A = (size_t)p.A;
+    int i = 0;
+    for (int f = 0; f < HW_WORDS; ++f, ++i) row[i] = 4u * (uint32_t)p.H, base[i] = (uint8_t *)(p.hum + (size_t)f * A * p.H);
+    for (int f = 0; f < ZW_WORDS; ++f, ++i) row[i] = 4u * (uint32_t)p.Z, base[i] = (uint8_t *)(p.zom + (size_t)f * A * p.Z);
+    for (int f = 0; f < BW_WORDS; ++f, ++i) row[i] = 4u * (uint32_t)p.B, base[i] = (uint8_t *)(p.bul + (size_t)f * A * p.B);
+    row[i] = 4u * (uint32_t)p.P, base[i++] = (uint8_t *)p.por;
+    row[i] = 4u * RNG_WORDS, base[i++] = (uint8_t *)p.rng;
+    row[i] = 4u * RNG_WORDS, base[i++] = (uint8_t *)p.rng2;
+    row[i] = (uint32_t)p.cells_pad, base[i++] = p.flags;
+    row[i] = 4u * (uint32_t)cells, base[i++] = (uint8_t *)p.aux_dmg;
+    row[i] = 2u * (uint32_t)cells, base[i++] = (uint8_t *)p.aux_pidx;
+  }
+  size_t snap_payload() const {  // bytes of one slot: every piece's row, then the scalar block
+    uint32_t row[SNAP_PIECES];
+    uint8_t *base[SNAP_PIECES];
+    snap_rows(row, base);
+    size_t n = (size_t)SC_WORDS * 4u;
+    for (int i = 0; i < SNAP_PIECES; ++i) n += row[i];
+    return n;
+  }
+  // Every configuration field that shapes or interprets an arena's state; not `arenas`, not `device`: a slot is one arena
+  uint64_t snap_fingerprint() const {
+    SnapHash h;
+    const int32_t dims[] = {p.F, p.N, p.M, p.H, p.Z, p.B, p.P, p.C, p.mode, p.level, p.n_agents, p.ind, p.auto_reset,
+                            p.reseed /* the effective stride */, p.timer_lim, cfg.timer_frames_per_level > 0 ? cfg.timer_frames_per_level : 7500,
+                            cfg.n_agent_profiles};
+    for (int32_t v : dims) h.word(v);
+    for (int i = 0; i < SF_MAX_AGENTS; ++i) h.word(tab.teams[i]);
+    auto words = [&](const void *q, size_t bytes) {
+      const int32_t *w = static_cast<const int32_t *>(q);
+      for (size_t i = 0; i < bytes / 4; ++i) h.word(w[i]);
+    };
+    words(&cfg.player, sizeof cfg.player), words(&cfg.npc, sizeof cfg.npc), words(&cfg.items, sizeof cfg.items);
+    for (int i = 0; i < cfg.n_agent_profiles; ++i) words(&cfg.agent_profile[i], sizeof cfg.agent_profile[i]);
+    h.bytes(map_flags.data(), (size_t)cells);
+    for (int i = 0; i < cells; ++i) h.word(map_pidx[i]);
+    for (int i = 0; i < p.P; ++i) h.word(map_exits[i]);
+    return h.finish();
+  }
+  struct Snapshot {
+    Env *owner = nullptr;
+    int32_t slots = 0, parts = 1;
+    uint8_t *block = nullptr;  // one allocation: every piece's [slots] rows, the scalar blocks, valid words, counters
+    Snap k;                    // the launch's argument but for slot_of_arena
+    size_t payload = 0;
+  };
+  int snapshot_slot_bytes(int64_t *device_bytes, int64_t *blob_bytes) const {
+    if (!device_bytes && !blob_bytes) return fail(SF_ERR_ARG, "sf_snapshot_slot_bytes: null outputs");
+    if (device_bytes) *device_bytes = (int64_t)snap_payload() + 4;  // (+ the valid word)
+    if (blob_bytes) *blob_bytes = (int64_t)snap_payload() + SNAP_BLOB_HEADER;
+    return SF_OK;
+  }
+  int snapshot_create(int32_t slots, Snapshot **out) {
+    if (!out) return fail(SF_ERR_ARG, "sf_snapshot_create: null output handle");
+    *out = nullptr;
+    if (slots < 1) return fail(SF_ERR_ARG, "sf_snapshot_create: slots < 1");
+    Snapshot *s = new (std::nothrow) Snapshot();
+    if (!s) return fail(SF_ERR_MEMORY, "host allocation failed");
+    s->owner = this, s->slots = slots, s->payload = snap_payload(), s->parts = snap_parts_for(s->payload);
+    uint32_t row[SNAP_PIECES];
+    uint8_t *base[SNAP_PIECES];
+    snap_rows(row, base);
+    size_t off[SNAP_PIECES], at = 0;
+    for (int i = 0; i < SNAP_PIECES; ++i) off[i] = at, at = (at + (size_t)slots * row[i] + 255u) & ~(size_t)255u;
+    const size_t scal_at = at, valid_at = scal_at + (size_t)slots * SC_WORDS * 4u, count_at = valid_at + (size_t)slots * 4u;
+    const size_t total = count_at + SNAP_COUNTERS * 4u;
+    if (int rc = alloc(s->block, total)) {
+      delete s;
+      return rc;
+    }
+    memset(&s->k, 0, sizeof s->k);
+    for (int i = 0; i < SNAP_PIECES; ++i)
+      s->k.piece[i] = SnapPiece{base[i], s->block + off[i], row[i], snap_part_bytes(row[i], s->parts), snap_width_for(row[i]), 0u};
+    s->k.scal_env = p.scal, s->k.scal_snap = reinterpret_cast<int32_t *>(s->block + scal_at);
+    s->k.valid = reinterpret_cast<int32_t *>(s->block + valid_at);
+    s->k.counters = reinterpret_cast<uint32_t *>(s->block + count_at);
+    s->k.A = p.A, s->k.slots = slots;
+    rt.zero(s->block + valid_at, total - valid_at);  // every slot empty, the counters at 0
+    if (int rc = rt.sync()) {
+      rt.free(s->block);
+      delete s;
+      return rc;
+    }
+    *out = s;
+    return SF_OK;
+  }
+  int snapshot_destroy(Snapshot *s) {
+    if (!s) return SF_OK;
+    int rc = rt.sync();  // launches still in flight may read or write the slots
+    rt.free(s->block);
+    delete s;
+    return rc;
+  }
+  // one stream-ordered launch; nothing is allocated, copied or waited for
+  int snapshot_copy(Snapshot *s, const int32_t *d_slot_of_arena, bool save) {
+    const std::string who = save ? "sf_snapshot_save" : "sf_snapshot_load";
+    if (!s || !d_slot_of_arena) return fail(SF_ERR_ARG, who + ": null argument");
+    if (s->owner != this) return fail(SF_ERR_STATE, who + ": the snapshot was created for another environment");
+    if (!was_reset) return fail(SF_ERR_STATE, who + " before sf_reset");
+    if (int rc = not_mid_step(who.c_str())) return rc;
+    if (rp.status) return fail(SF_ERR_STATE, who + " while a replay is loaded (sf_replay_load)");
+    Snap k = s->k;
+    k.slot_of_arena = d_slot_of_arena;
+    if (int rc = rt.launch_snapshot(k, s->parts, save)) return rc;
+    if (!save) steps_since_rank = 1 << 30;  // the populations the launch order was built from are gone
+    return SF_OK;
+  }
+  int snapshot_status(Snapshot *s, int32_t out[4]) {
+    if (!s || !out) return fail(SF_ERR_ARG, "sf_snapshot_status: null argument");
+    rt.d2h(out, s->k.counters, SNAP_COUNTERS * sizeof(int32_t));
+    rt.zero(s->k.counters, SNAP_COUNTERS * sizeof(int32_t));
+    return rt.sync();
+  }
+  int snapshot_slot_check(const Snapshot *s, int32_t slot, const void *blob, int64_t bytes, const char *who) const {
+    if (!s || !blob) return fail(SF_ERR_ARG, std::string(who) + ": null argument");
+    if (slot < 0 || slot >= s->slots) return fail(SF_ERR_ARG, std::string(who) + ": slot out of range");
+    if (bytes < SNAP_BLOB_HEADER + (int64_t)s->payload) return fail(SF_ERR_ARG, std::string(who) + ": " + snap_blob_message(SNAP_BLOB_SHORT));
+    return SF_OK;
+  }
+  int snapshot_export(Snapshot *s, int32_t slot, void *blob, int64_t bytes) {
+    if (int rc = snapshot_slot_check(s, slot, blob, bytes, "sf_snapshot_export")) return rc;
+    int32_t valid = 0;
+    rt.d2h(&valid, s->k.valid + slot, sizeof valid);
+    if (int rc = rt.sync()) return rc;
+    if (!valid) return fail(SF_ERR_STATE, "sf_snapshot_export: the slot was never saved or imported");
+    uint8_t *out = static_cast<uint8_t *>(blob);
+    snap_blob_header(out, s->payload, snap_fingerprint());
+    out += SNAP_BLOB_HEADER;
+    for (int i = 0; i < SNAP_PIECES; ++i) {
+      const SnapPiece &pc = s->k.piece[i];
+      rt.d2h(out, pc.snap + (size_t)slot * pc.row_bytes, pc.row_bytes);
+      out += pc.row_bytes;
+    }
+    rt.d2h(out, s->k.scal_snap + (size_t)slot * SC_WORDS, SC_WORDS * 4u);
+    return rt.sync();
+  }
+  int snapshot_import(Snapshot *s, int32_t slot, const void *blob, int64_t bytes) {
+    if (!s || !blob) return fail(SF_ERR_ARG, "sf_snapshot_import: null argument");
+    if (slot < 0 || slot >= s->slots) return fail(SF_ERR_ARG, "sf_snapshot_import: slot out of range");
+    if (int v = snap_blob_check(blob, bytes, s->payload, snap_fingerprint()))
+      return fail(SF_ERR_ARG, std::string("sf_snapshot_import: ") + snap_blob_message(v));
+    const uint8_t *in = static_cast<const uint8_t *>(blob) + SNAP_BLOB_HEADER;
+    for (int i = 0; i < SNAP_PIECES; ++i) {
+      const SnapPiece &pc = s->k.piece[i];
+      rt.h2d(pc.snap + (size_t)slot * pc.row_bytes, in, pc.row_bytes);
+      in += pc.row_bytes;
+    }
+    rt.h2d(s->k.scal_snap + (size_t)slot * SC_WORDS, in, SC_WORDS * 4u);
+    const int32_t one = 1;
+    rt.h2d(s->k.valid + slot, &one, sizeof one);
+    return rt.sync();  // (the caller's buffer and `one` are free again)
   }
 
   // ---- parity tooling ----------------------------------------------------------------------------

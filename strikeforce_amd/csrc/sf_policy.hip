@@ -543,6 +543,7 @@ static int forward(Policy *p, int agents, const ForwardReq &r) {
 }  // namespace sfp
 
 #include "sf_policy_load.hpp"
+#include "sf_policy_memory.hpp"
 
 using sfp::Policy;
 
@@ -745,6 +746,11 @@ int sf_policy_set_memory(sf_policy *pp, int32_t agent, const float *h, const flo
     SFP_HIP(hipMemcpy(p->h[g] + (size_t)agent * sfp::HID, h + g * sfp::HID, sfp::HID * sizeof(float), hipMemcpyHostToDevice));
   SFP_HIP(hipMemcpy(p->action_input + (size_t)agent * sfp::ACT, action_input, sfp::ACT * sizeof(float), hipMemcpyHostToDevice));
   return SF_OK;
+}
+
+int sf_policy_memory_rows(sf_policy *pp, int32_t to_rows, float *d_h, float *d_action, const int32_t *d_row_of_agent, int32_t rows,
+                          int32_t agents) {
+  return sfp::memory_rows(reinterpret_cast<Policy *>(pp), to_rows, d_h, d_action, d_row_of_agent, rows, agents);
 }
 
 int sf_policy_set_stream(sf_policy *pp, void *hip_stream) {

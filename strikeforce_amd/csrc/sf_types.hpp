@@ -141,6 +141,42 @@ struct ResetSel {
   uint8_t *selected;       // null, or [A][n_agents]: 1 for every agent of a restarted arena, else 0
 };
 
+// ---- arena snapshots (sf_snapshot_save / sf_snapshot_load, sf_snapshot.hpp snapshot_body) --------------------------
+// What k_snapshot takes, by value in the kernel arguments.  A struct of its own, like Replay and ResetSel: Params stays as
+// it is.  One piece per row an arena owns in a state buffer — the 13 + 3 + 4 fields of hum / zom / bul, por, rng, rng2,
+// flags, aux_dmg, aux_pidx — arena a's row at env + a * row_bytes, slot s's at snap + s * row_bytes: the snapshot has the
+// environment's [field][slot][entity] layout, so both sides of a copy coalesce the same way.  scal travels apart (a load
+// keeps the destination's SC_EPISODES).
+constexpr int SNAP_PIECES = HW_WORDS + ZW_WORDS + BW_WORDS + 6;
+enum { SNAP_EMPTY = 0, SNAP_RANGE, SNAP_COUNTERS = 4 };  // the snapshot's device counters (sf_snapshot_status)
+struct SnapPiece {
+  uint8_t *env;        // the field's row of arena 0
+  uint8_t *snap;       // ... and of slot 0
+  uint32_t row_bytes;  // one arena's row
+  uint32_t part_bytes; // what one wavefront of the arena's `parts` copies of the row: a multiple of 1024, 0 for no row
+  uint32_t width;      // bytes per lane and access: 16 where row_bytes is a multiple of 16, else 4, else 2
+  uint32_t pad;
+};
+struct Snap {
+  SnapPiece piece[SNAP_PIECES];
+  int32_t *scal_env, *scal_snap;   // [A][SC_WORDS], [slots][SC_WORDS]
+  const int32_t *slot_of_arena;    // [A]: -1 = the arena takes no part
+  int32_t *valid;                  // [slots]: 1 once the slot holds a state
+  uint32_t *counters;              // [SNAP_COUNTERS]: arenas skipped for an empty slot, for an index out of range, 0, 0
+  int32_t A, slots;
+};
+
+// how an arena's rows are split over wavefronts: parts of about 16 KiB of the state's bytes, at most 64 of them
+inline int snap_parts_for(size_t slot_bytes) {
+  const size_t n = (slot_bytes + 16u * 1024u - 1u) / (16u * 1024u);
+  return n < 1 ? 1 : n > 64 ? 64 : (int)n;
+}
+inline uint32_t snap_part_bytes(uint32_t row_bytes, int parts) {
+  const uint32_t per = (row_bytes + (uint32_t)parts - 1u) / (uint32_t)parts;
+  return (per + 1023u) & ~1023u;
+}
+inline uint32_t snap_width_for(uint32_t row_bytes) { return row_bytes % 16u == 0u ? 16u : row_bytes % 4u == 0u ? 4u : 2u; }
+
 // ---- everything a kernel needs -----------------------------------------------------------------------
 struct Params {
   int32_t A, F, N, M, cells, cells_pad;

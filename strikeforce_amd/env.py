@@ -72,6 +72,8 @@ def load_library():
         if hasattr(L, "sf_reset_arenas"):  # (restart of chosen arenas; an older build loaded through SF_LIBRARY_PATH lacks it)
             L.sf_reset_arenas.argtypes = [vp, C.POINTER(abi.ResetSel)]
             L.sf_reset_arenas.restype = C.c_int
+        if hasattr(L, "sf_snapshot_create"):  # (arena snapshots; an older build loaded through SF_LIBRARY_PATH lacks them)
+            abi.bind_snapshot(L, "sf_")
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -109,7 +111,7 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
            "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device",
-           "sf_reset_arenas"]
+           "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -131,6 +133,81 @@ def decode_episodes(records, n_agents):
         "steps": r[:, 6].copy(), "outcome": r[:, 7].copy(),
         "results": r[:, EPISODE_HDR_WORDS:].reshape(-1, n_agents, 8).copy(),
     }
+
+
+class Snapshot:
+    """`slots` saved arena states in device memory (strikeforce.h sf_snapshot_*): save(slot_of_arena) copies arena a into
+    slot slot_of_arena[a], load(slot_of_arena) copies slot slot_of_arena[a] into arena a; -1 leaves the arena out, and many
+    arenas may load one slot — the fork.  Both are one stream-ordered launch.  slot_of_arena: a device address (int) of
+    int32 [arenas], a torch int32 tensor on the environment's device, or a host array, which is uploaded first (and, for
+    save, refused if two arenas name one slot).  A load keeps the destination's episode count, result latch and episode
+    log; what else it carries and leaves is in the header.  export / import_ move one slot through a host blob that only
+    an environment of the same configuration (any arena count) accepts.  close() before the environment's."""
+
+    def __init__(self, batch, slots):
+        if not hasattr(batch.L, "sf_snapshot_create"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_snapshot_* entry points")
+        self.batch, self.L, self.slots = batch, batch.L, int(slots)
+        self.h = C.c_void_p()
+        self._held = None  # the uploaded index array of the last call: alive until the next one replaces it
+        rc = self.L.sf_snapshot_create(batch.h, self.slots, C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            raise StrikeForceError("sf_snapshot_create failed (%d): %s" % (rc, self.L.sf_last_error().decode()))
+        self.blob_bytes = batch.snapshot_slot_bytes()[1]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.sf_snapshot_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _index(self, slot_of_arena, saving):
+        if isinstance(slot_of_arena, int):
+            return slot_of_arena
+        if hasattr(slot_of_arena, "data_ptr"):  # a torch tensor
+            t = slot_of_arena
+            if str(t.dtype) != "torch.int32" or not t.is_cuda or not t.is_contiguous() or t.numel() != self.batch.cfg.arenas:
+                raise ValueError("slot_of_arena must be a contiguous int32 tensor of `arenas` entries on the device")
+            return t.data_ptr()
+        host = np.ascontiguousarray(slot_of_arena, dtype=np.int32).reshape(-1)
+        if host.size != self.batch.cfg.arenas:
+            raise ValueError("slot_of_arena must hold one entry per arena")
+        named = host[(host >= 0) & (host < self.slots)]  # (anything else is skipped by the kernel)
+        if saving and len(np.unique(named)) != len(named):
+            raise ValueError("two arenas save into one slot")
+        import torch
+        # (a copy from pageable host memory has arrived when .to() returns, whatever stream the environment runs on)
+        self._held = torch.from_numpy(host).to("cuda:%d" % self.batch.cfg.device)
+        return self._held.data_ptr()
+
+    def save(self, slot_of_arena):
+        rc = self.L.sf_snapshot_save(self.batch.h, self.h, C.c_void_p(self._index(slot_of_arena, True)))
+        self.batch._ck(rc, "sf_snapshot_save")
+
+    def load(self, slot_of_arena):
+        rc = self.L.sf_snapshot_load(self.batch.h, self.h, C.c_void_p(self._index(slot_of_arena, False)))
+        self.batch._ck(rc, "sf_snapshot_load")
+
+    def status(self):
+        """(arenas skipped for an empty slot, arenas skipped for an index out of range) since the last call; synchronises."""
+        out = (C.c_int32 * abi.SNAPSHOT_STATUS_WORDS)()
+        self.batch._ck(self.L.sf_snapshot_status(self.h, C.byref(out)), "sf_snapshot_status")
+        return int(out[0]), int(out[1])
+
+    def export(self, slot):
+        buf = C.create_string_buffer(self.blob_bytes)
+        self.batch._ck(self.L.sf_snapshot_export(self.h, int(slot), C.cast(buf, C.c_void_p), self.blob_bytes), "sf_snapshot_export")
+        return buf.raw
+
+    def import_(self, slot, blob):
+        blob = bytes(blob)
+        self.batch._ck(self.L.sf_snapshot_import(self.h, int(slot), C.cast(C.c_char_p(blob), C.c_void_p), len(blob)), "sf_snapshot_import")
 
 
 class ArenaBatch:
@@ -188,6 +265,18 @@ class ArenaBatch:
             raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_reset_arenas")
         sel = abi.ResetSel(mask_ptr, int(mask_stride), 1 if done else 0, int(max_steps), tb_ptr, serial_ptr, selected_ptr)
         self._ck(self.L.sf_reset_arenas(self.h, C.byref(sel)), "sf_reset_arenas")
+
+    def snapshot(self, slots):
+        """Device memory for `slots` arena states of this configuration (sf_snapshot_create): see Snapshot."""
+        return Snapshot(self, slots)
+
+    def snapshot_slot_bytes(self):
+        """(device bytes, blob bytes) one snapshot slot of this configuration takes: to budget before snapshot()."""
+        if not hasattr(self.L, "sf_snapshot_create"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_snapshot_* entry points")
+        d, b = C.c_int64(0), C.c_int64(0)
+        self._ck(self.L.sf_snapshot_slot_bytes(self.h, C.byref(d), C.byref(b)), "sf_snapshot_slot_bytes")
+        return int(d.value), int(b.value)
 
     def step(self, cmd):
         cmd = np.ascontiguousarray(cmd, dtype=np.uint8)

@@ -215,6 +215,8 @@ def _bind(L):
     if hasattr(L, "sf_policy_load_weights"):  # (parameters in, from the device: _NetBatch.load_weights)
         L.sf_policy_load_weights.argtypes = [vp, C.POINTER(Weights)]
         L.sf_policy_weights_digest.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]
+    if hasattr(L, "sf_policy_memory_rows"):  # (an older build loaded through SF_LIBRARY_PATH lacks it)
+        L.sf_policy_memory_rows.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, C.c_int32]
     for n in EXPORTS + REWARD_EXPORTS:
         if n != "sf_policy_destroy" and hasattr(L, n):
             getattr(L, n).restype = C.c_int
@@ -227,7 +229,7 @@ EXPORTS = ["sf_policy_create", "sf_policy_destroy", "sf_policy_reset_memory", "s
            "sf_policy_sparse_overflows", "sf_policy_act", "sf_policy_predict_sparse",
            "sf_policy_get_memory", "sf_policy_set_memory", "sf_policy_set_stream", "sf_policy_synchronize",
            "sf_policy_kernel_time", "sf_policy_kernel_time_ex", "sf_policy_kernel_time_by_kernel", "sf_policy_gemm", "sf_policy_gemm_split", "sf_policy_features", "sf_policy_abi_version",
-           "sf_policy_update_actions", "sf_policy_load_weights", "sf_policy_weights_digest"]
+           "sf_policy_update_actions", "sf_policy_load_weights", "sf_policy_weights_digest", "sf_policy_memory_rows"]
 
 
 # the reward network's entries (sf_reward_*: the same header)
@@ -329,6 +331,17 @@ class _NetBatch:
         a = np.ascontiguousarray(action_input, dtype=np.float32).reshape(ACTIONS)
         self._ck(self.L.sf_policy_set_memory(self.h, int(agent), h.ctypes.data_as(_FP), a.ctypes.data_as(_FP)),
                  "sf_policy_set_memory")
+
+    def memory_rows(self, to_rows, d_h_ptr, d_action_ptr, d_row_of_agent_ptr, rows, agents=None):
+        """The memory of agents [0, agents) to (to_rows=True) or from rows of the caller's device buffers, one stream-ordered
+        launch (sf_policy_memory_rows): d_h float32 [rows][2][160], d_action float32 [rows][9], d_row_of_agent int32
+        [agents] with -1 (or anything outside [0, rows)) for an agent that takes no part.  Many agents may read one row:
+        the network memory of a forked arena (env.Snapshot.load)."""
+        if not hasattr(self.L, "sf_policy_memory_rows"):
+            raise env.StrikeForceError("this build of libstrikeforce_amd.so has no sf_policy_memory_rows")
+        n = self.max_agents if agents is None else int(agents)
+        self._ck(self.L.sf_policy_memory_rows(self.h, 1 if to_rows else 0, C.c_void_p(d_h_ptr), C.c_void_p(d_action_ptr),
+                                              C.c_void_p(d_row_of_agent_ptr), int(rows), n), "sf_policy_memory_rows")
 
     def kernel_time_by_pipe(self, enable=True):
         """[(ms, flop, launches) of the f32-MFMA launches, (...) of the bf16-split launches] since the last call."""
