@@ -255,6 +255,95 @@ int sf_snapshot_status(sf_snapshot *s, int32_t out_host[4]);   /* skipped: empty
 int sf_snapshot_export(sf_snapshot *s, int32_t slot, void *blob_host, int64_t bytes);        /* one slot -> host blob */
 int sf_snapshot_import(sf_snapshot *s, int32_t slot, const void *blob_host, int64_t bytes);  /* host blob -> one slot */
 
+/* ---- per-step game signals and a shaped reward, on the device ------------------------------------------------------
+ * The reference keeps `kills / teams_kills / loot` per game (gameplay.hpp:461, counted up in hit_human and hit_zombie,
+ * gameplay.hpp:588-593,625-629) and `kills / damage / effect` per human (Character.hpp:294) up to date every tick; Hp,
+ * stamina and mindamage are the human's own fields (Character.hpp:286-293).  sf_results shows them once per game and
+ * sf_dump_arena one arena at a time through the host.  sf_signals_step hands them out behind any step, for every (arena,
+ * agent) at once and without leaving the device: their levels now (vitals), their change since the previous call on the
+ * same signals object (delta), and a weighted sum of that change (reward) in the layout sf_rollout_step.d_reward takes.
+ * It writes nothing of the environment: digests, dumps and the next step are as without the call.
+ * A signals object belongs to one environment and owns, in device memory, one baseline per (arena, agent): the arena's
+ * seed, step count, episode count and done flag, the agent's six counters (sf_results' words 0..5) and whether it was
+ * present, all as of the previous call.
+ *
+ * Vitals, SF_VITALS_WORDS x int32:  flags, hp, stamina, mindamage, kills, damage, effect, floor, row, col, way, team |
+ *   arena kills, teams_kills, loot, steps.  Words 1..11 are what sf_dump_arena shows for human slot g (Character.hpp:
+ *   286-294, position and way gameplay.hpp:43) and are 0 for an agent that is not present; words 12..15 are
+ *   sf_arena_hdr's (gameplay.hpp:461).
+ * Delta, SF_DELTA_WORDS x int32:  flags, d kills, d teams_kills, d loot, d damage, d effect, d Hp, outcome — the
+ *   differences of sf_results' words 0..5; outcome is an SF_* outcome code, 0 unless SF_SIG_ENDED is set.
+ * Both carry the same flag word:
+ *   SF_SIG_PRESENT     alive and commanded now: sf_agent_alive's bit (Character.hpp:291,333-338)
+ *   SF_SIG_DIED        present at the previous call, gone now, and its game was not ended by that (hit_human's
+ *                      deleteAgent, gameplay.hpp:648-649)
+ *   SF_SIG_ENDED       this agent's game ended since the previous call (check_end, gameplay.hpp:1102-1229,1450)
+ *   SF_SIG_REBASED     rule 1 below: the baseline was set anew, deltas and reward are 0
+ *   SF_SIG_UNRESOLVED  rule 2, or a death that rule 4 cannot attribute
+ *   SF_SIG_IDLE        the arena stands still: done, and already done at the previous call; the reward is 0
+ * Rules, per arena in this order; n = sf_arena_hdr.episodes now - in the baseline.  After every rule the baseline becomes
+ * the current state.
+ *   1. Rebase: the first call after create; the agent's d_rebase byte set; n < 0 (a whole sf_reset); n == 0 with another
+ *      (tb, serial) or with fewer steps than the baseline's (an sf_reset_arenas or sf_snapshot_load the caller did not
+ *      announce).  Flags REBASED (and PRESENT), deltas 0.  d_rebase is authoritative: pass sf_reset_sel.d_selected, or
+ *      the agents of the arenas an sf_snapshot_load named.  The detection is a guard, and what it catches is counted; it
+ *      cannot see a whole sf_reset onto the running seed before the first game has ended, nor a load of the arena's OWN
+ *      state of the same game with a step count that is not below the baseline's (a save, steps, load, the same number of
+ *      steps again): such calls read as one game going on, with the differences of the counters as deltas.
+ *   2. n >= 2: several games ended inside one launch (sf_step_device with k > 1 under auto_reset).  Flags ENDED |
+ *      UNRESOLVED, deltas 0, outcome the latch's (the last game's).  The episode log has every one of those games.
+ *   3. n == 1: the ended game's last values are its row of the result latch (sf_results), whether or not the arena has
+ *      restarted since.  Agents present in the baseline: delta = latch - baseline.  Flags ENDED, outcome = latch word 7.
+ *      The latch row of a commanded human other than `ind` holds whatever stands in its slot when the game ends
+ *      (sf_results' own rule): a human that died in that very step still shows its corpse, one whose slot a spawned NPC
+ *      took shows the NPC.
+ *   4. n == 0, the same game.  An agent present in the baseline and
+ *        - still present: delta = current - baseline, PRESENT;
+ *        - gone, its slot not alive, exactly one step since the baseline: the row is its own corpse's: delta = current -
+ *          baseline, DIED;
+ *        - gone otherwise (the slot alive again: h_ind handed it to a spawned NPC, gameplay.hpp:216-221; or several steps
+ *          passed, in which that may have happened and ended again): d kills, d damage, d effect 0, d teams_kills and d
+ *          loot current - baseline (they are the arena's), d Hp = -(baseline Hp); DIED, and UNRESOLVED if more than one
+ *          step passed.
+ *      An agent not present in the baseline has all-zero deltas (under rules 2 and 3 it still gets ENDED and the outcome).
+ *      A replayed arena whose stream ran out (sf_replay_step: done newly set, no episode counted) reports ENDED with
+ *      outcome SF_SAMPLE_END beside the above.
+ * Reward, float32, separate multiplies and adds in this order, nothing fused:
+ *      r = 0
+ *      if present in the baseline:  r = per_step;  for j in 0..5:  r = r + w[j] * (float)delta[j]
+ *      if DIED:  r = r + died
+ *      if ENDED and present in the baseline and not UNRESOLVED:  r = r + outcome[code]
+ *   and 0 under REBASED and IDLE.
+ * sf_signals_step is one kernel launch in stream order on the environment's stream: no allocation, no copy, no host
+ * synchronisation; the struct travels in the kernel arguments (it may be a temporary) and the call may be captured in a
+ * graph behind sf_step_device.  create, destroy and status synchronise.  Destroy a signals object before its environment.
+ * sf_signals_status: how many delta records carried UNRESOLVED, how many were rebased by the detection alone (valid
+ * baseline, d_rebase byte clear), 0, 0, since create or the last status call; it clears the counters.
+ * SF_ERR_STATE: before the first sf_reset, between sf_step_begin and sf_step_end, a signals object of another environment.
+ * SF_ERR_ARG: null handles, or a non-NULL pointer that is not device memory of the environment's device, is not aligned
+ * (4 bytes; d_rebase 1) or whose extent reaches past its allocation; nothing is launched then. */
+#define SF_VITALS_WORDS 16
+#define SF_DELTA_WORDS 8
+enum { SF_SIG_PRESENT = 1, SF_SIG_DIED = 2, SF_SIG_ENDED = 4, SF_SIG_REBASED = 8, SF_SIG_UNRESOLVED = 16, SF_SIG_IDLE = 32 };
+typedef struct sf_signals sf_signals;          /* opaque; belongs to one env; owns a per-(arena, agent) baseline on the device */
+int sf_signals_create(sf_env *env, sf_signals **out);
+int sf_signals_destroy(sf_signals *s);         /* before its env */
+typedef struct sf_reward_weights {             /* travels by value in the kernel arguments */
+  float per_step;                              /* for an agent that was present at the previous call */
+  float w[6];                                  /* kills, teams_kills, loot, damage, effect, Hp: sf_results' words 0..5 */
+  float died;                                  /* added on SF_SIG_DIED */
+  float outcome[8];                            /* by SF_* outcome code, added on SF_SIG_ENDED */
+} sf_reward_weights;
+typedef struct sf_signals_io {
+  int32_t *d_vitals;         /* optional, [arenas][n_agents][SF_VITALS_WORDS] */
+  int32_t *d_delta;          /* optional, [arenas][n_agents][SF_DELTA_WORDS] */
+  float   *d_reward;         /* optional, [arenas * n_agents]: the layout sf_rollout_step.d_reward takes */
+  const uint8_t *d_rebase;   /* optional, [arenas][n_agents] (sf_reset_sel.d_selected's layout): != 0 -> rule 1 */
+  sf_reward_weights weights; /* read only when d_reward != NULL */
+} sf_signals_io;
+int sf_signals_step(sf_env *env, sf_signals *s, const sf_signals_io *io);
+int sf_signals_status(sf_signals *s, int64_t out_host[4]);   /* unresolved, rebased by detection, 0, 0; synchronises; clears */
+
 /* One iteration of gameplay::play()'s while(true) body, gameplay.hpp:1452-1471, followed by the next
  * iteration's loop-top (spawns + check_end, gameplay.hpp:1444-1450), for every arena.
  * cmd: host array [arenas][n_agents] of reference command chars (valid_commands gameplay.hpp:45, plus

@@ -163,6 +163,39 @@ def bind_snapshot(lib, prefix):
     return lib
 
 
+VITALS_WORDS, DELTA_WORDS = 16, 8  # SF_VITALS_WORDS, SF_DELTA_WORDS
+SIG_PRESENT, SIG_DIED, SIG_ENDED, SIG_REBASED, SIG_UNRESOLVED, SIG_IDLE = 1, 2, 4, 8, 16, 32  # SF_SIG_*
+VITALS_FIELDS = ("flags", "hp", "stamina", "mindamage", "kills", "damage", "effect", "floor", "row", "col", "way", "team",
+                 "arena_kills", "teams_kills", "loot", "steps")
+DELTA_FIELDS = ("flags", "d_kills", "d_teams_kills", "d_loot", "d_damage", "d_effect", "d_hp", "outcome")
+SIGNALS_STATUS_WORDS = 4  # sf_signals_status: records with UNRESOLVED, records rebased by the detection alone, 0, 0
+SIGNALS_EXPORTS = ("signals_create", "signals_destroy", "signals_step", "signals_status")
+
+
+class RewardWeights(C.Structure):
+    """sf_reward_weights: per_step, w[6] over sf_results' words 0..5, died, outcome[8] by SF_* outcome code."""
+    _fields_ = [("per_step", C.c_float), ("w", C.c_float * 6), ("died", C.c_float), ("outcome", C.c_float * 8)]
+
+
+class SignalsIO(C.Structure):
+    """sf_signals_io: the optional outputs and the rebase mask of one sf_signals_step (device pointers as integers)."""
+    _fields_ = [("d_vitals", C.c_void_p), ("d_delta", C.c_void_p), ("d_reward", C.c_void_p), ("d_rebase", C.c_void_p),
+                ("weights", RewardWeights)]
+
+
+def bind_signals(lib, prefix):
+    """Declare the sf_signals_* entry points (strikeforce.h) on a loaded library; handles and pointers as integers."""
+    g = lambda n: getattr(lib, prefix + n)
+    vp = C.c_void_p
+    g("signals_create").argtypes = [vp, C.POINTER(vp)]
+    g("signals_destroy").argtypes = [vp]
+    g("signals_step").argtypes = [vp, vp, C.POINTER(SignalsIO)]
+    g("signals_status").argtypes = [vp, C.POINTER(C.c_int64 * SIGNALS_STATUS_WORDS)]
+    for n in SIGNALS_EXPORTS:
+        g(n).restype = C.c_int
+    return lib
+
+
 def struct_to_dict(s):
     out = {}
     for name, _ in s._fields_:

@@ -5,6 +5,7 @@
 //     configuration's fields as constants: sf_types.hpp FixedShapes), k_agent_alive, k_done, k_ep_late, k_replay_fetch
 //   k_rank (k_step's launch order) and the episode-log collection kernels k_ep_plan / k_ep_copy
 //   k_snapshot<SAVE>, the copy between the state buffers and a snapshot object (sf_snapshot.hpp)
+//   k_signals, vitals / delta / reward per (arena, agent) behind a step (sf_signals.hpp)
 //   HipRT, the runtime Env<RT> (sf_host.hpp) launches through
 //   Comm, the RCCL exchange of the multi-GPU path
 //   the extern "C" entry points
@@ -26,6 +27,7 @@
 #include "sf_obs.hpp"
 #include "sf_obs_kernels.hpp"
 #include "sf_snapshot.hpp"
+#include "sf_signals.hpp"
 #include "sf_host.hpp"
 // clang-format on
 
@@ -257,6 +259,13 @@ __global__ __launch_bounds__(64) void k_snapshot(Snap s) {
   SnapCore<SnapGfx950, SAVE>::body(s, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+// sf_signals_step (sf_signals.hpp): one lane per (arena, agent), like k_agent_alive and k_done, whose rows it reads.
+__global__ __launch_bounds__(256) void k_signals(Signals s) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= s.A * s.n_agents) return;
+  signals_agent(s, i);
+}
+
 #define SF_HIP(call)                                                                       \
   do {                                                                                     \
     hipError_t e_ = (call);                                                                \
@@ -356,6 +365,17 @@ struct HipRT {
       return rc;
     const dim3 grid((unsigned)k.A, (unsigned)parts);
     return save ? launch(k_snapshot<true>, grid, dim3(64), 0, k) : launch(k_snapshot<false>, grid, dim3(64), 0, k);
+  }
+  // sf_signals_step: one launch; the optional pointers are checked as sf_reset_arenas checks its own
+  int launch_signals(const Signals &k) {
+    SF_HIP(hipSetDevice(device));
+    const size_t n = (size_t)k.A * (size_t)k.n_agents;
+    int rc;
+    if (k.vitals && (rc = check_device_range(k.vitals, n * SF_VITALS_WORDS * sizeof(int32_t), 4, "d_vitals", "sf_signals_step"))) return rc;
+    if (k.delta && (rc = check_device_range(k.delta, n * SF_DELTA_WORDS * sizeof(int32_t), 4, "d_delta", "sf_signals_step"))) return rc;
+    if (k.reward && (rc = check_device_range(k.reward, n * sizeof(float), 4, "d_reward", "sf_signals_step"))) return rc;
+    if (k.rebase && (rc = check_device_range(k.rebase, n, 1, "d_rebase", "sf_signals_step"))) return rc;
+    return launch(k_signals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k);
   }
   bool can_rank() const { return true; }
   // k_rank runs right in front of the k_step launch it orders, inside that launch's pair of timing events: what
@@ -596,6 +616,9 @@ struct sf_env {
 struct sf_snapshot {
   sf::Env<sf::HipRT>::Snapshot *s;
 };
+struct sf_signals {
+  sf::Env<sf::HipRT>::SignalsObj *s;
+};
 
 using sf::fail;  // SF_HIP in the entry points below
 
@@ -683,6 +706,33 @@ int sf_snapshot_export(sf_snapshot *s, int32_t slot, void *blob_host, int64_t by
 int sf_snapshot_import(sf_snapshot *s, int32_t slot, const void *blob_host, int64_t bytes) {
   SF_SNAP(s);
   return s->s->owner->snapshot_import(s->s, slot, blob_host, bytes);
+}
+int sf_signals_create(sf_env *env, sf_signals **out) {
+  if (!out) return sf::fail(SF_ERR_ARG, "sf_signals_create: null output handle");
+  *out = nullptr;
+  SF_ENV(env);
+  sf_signals *h = new (std::nothrow) sf_signals{nullptr};
+  if (!h) return sf::fail(SF_ERR_MEMORY, "host allocation failed");
+  if (int rc = env->e.signals_create(&h->s)) {
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return SF_OK;
+}
+int sf_signals_destroy(sf_signals *s) {
+  if (!s) return SF_OK;
+  const int rc = s->s->owner->signals_destroy(s->s);
+  delete s;
+  return rc;
+}
+int sf_signals_step(sf_env *env, sf_signals *s, const sf_signals_io *io) {
+  SF_ENV(env);
+  return env->e.signals_step(s ? s->s : nullptr, io);
+}
+int sf_signals_status(sf_signals *s, int64_t out_host[4]) {
+  if (!s) return sf::fail(SF_ERR_ARG, "null signals object");
+  return s->s->owner->signals_status(s->s, out_host);
 }
 int sf_step(sf_env *env, const uint8_t *cmd) {
   SF_ENV(env);

@@ -20,6 +20,7 @@
 #include "sf_types.hpp"
 #include "sf_obs.hpp"
 #include "sf_snapshot_blob.hpp"
+#include "sf_signals.hpp"
 
 namespace sf {
 
@@ -938,6 +939,67 @@ struct Env {
     const int32_t one = 1;
     rt.h2d(s->k.valid + slot, &one, sizeof one);
     return rt.sync();  // (the caller's buffer and `one` are free again)
+  }
+
+  // ---- per-step signals (sf_signals_*; the per-agent body is sf_signals.hpp signals_agent, k_signals) -----------------
+  struct SignalsObj {
+    Env *owner = nullptr;
+    int32_t *base = nullptr;                // [A * n_agents][SIG_BASE_WORDS], all zero = no baseline yet
+    unsigned long long *counters = nullptr; // [SIG_COUNTERS]
+  };
+  int signals_create(SignalsObj **out) {
+    if (!out) return fail(SF_ERR_ARG, "sf_signals_create: null output handle");
+    *out = nullptr;
+    SignalsObj *s = new (std::nothrow) SignalsObj();
+    if (!s) return fail(SF_ERR_MEMORY, "host allocation failed");
+    s->owner = this;
+    const size_t words = (size_t)p.A * (size_t)p.n_agents * SIG_BASE_WORDS;
+    int rc;
+    if ((rc = alloc(s->base, words)) || (rc = alloc(s->counters, (size_t)SIG_COUNTERS))) {
+      if (s->base) rt.free(s->base);
+      delete s;
+      return rc;
+    }
+    rt.zero(s->base, words * sizeof(int32_t));
+    rt.zero(s->counters, SIG_COUNTERS * sizeof(unsigned long long));
+    if ((rc = rt.sync())) {
+      rt.free(s->base), rt.free(s->counters);
+      delete s;
+      return rc;
+    }
+    *out = s;
+    return SF_OK;
+  }
+  int signals_destroy(SignalsObj *s) {
+    if (!s) return SF_OK;
+    int rc = rt.sync();  // launches still in flight may read or write the baseline
+    rt.free(s->base), rt.free(s->counters);
+    delete s;
+    return rc;
+  }
+  // one stream-ordered launch; nothing is allocated, copied or waited for
+  int signals_step(SignalsObj *s, const sf_signals_io *io) {
+    if (!s || !io) return fail(SF_ERR_ARG, "sf_signals_step: null argument");
+    if (s->owner != this) return fail(SF_ERR_STATE, "sf_signals_step: the signals object was created for another environment");
+    if (!was_reset) return fail(SF_ERR_STATE, "sf_signals_step before sf_reset");
+    if (int rc = not_mid_step("sf_signals_step")) return rc;
+    Signals k;
+    memset(&k, 0, sizeof k);
+    k.hum = p.hum, k.scal = p.scal, k.results = p.results;
+    k.base = s->base, k.counters = s->counters;
+    k.vitals = io->d_vitals, k.delta = io->d_delta, k.reward = io->d_reward, k.rebase = io->d_rebase;
+    k.A = p.A, k.H = p.H, k.n_agents = p.n_agents;
+    if (io->d_reward) k.w = io->weights;
+    return rt.launch_signals(k);
+  }
+  int signals_status(SignalsObj *s, int64_t out[4]) {
+    if (!s || !out) return fail(SF_ERR_ARG, "sf_signals_status: null argument");
+    unsigned long long c[SIG_COUNTERS] = {0, 0, 0, 0};
+    rt.d2h(c, s->counters, sizeof c);
+    rt.zero(s->counters, sizeof c);
+    if (int rc = rt.sync()) return rc;
+    for (int i = 0; i < SIG_COUNTERS; ++i) out[i] = (int64_t)c[i];
+    return SF_OK;
   }
 
   // ---- parity tooling ----------------------------------------------------------------------------

@@ -74,6 +74,8 @@ def load_library():
             L.sf_reset_arenas.restype = C.c_int
         if hasattr(L, "sf_snapshot_create"):  # (arena snapshots; an older build loaded through SF_LIBRARY_PATH lacks them)
             abi.bind_snapshot(L, "sf_")
+        if hasattr(L, "sf_signals_create"):  # (per-step signals; an older build loaded through SF_LIBRARY_PATH lacks them)
+            abi.bind_signals(L, "sf_")
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -111,7 +113,7 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
            "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device",
-           "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS]
+           "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS + abi.SIGNALS_EXPORTS]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -210,6 +212,89 @@ class Snapshot:
         self.batch._ck(self.L.sf_snapshot_import(self.h, int(slot), C.cast(C.c_char_p(blob), C.c_void_p), len(blob)), "sf_snapshot_import")
 
 
+SIG_PRESENT, SIG_DIED, SIG_ENDED = abi.SIG_PRESENT, abi.SIG_DIED, abi.SIG_ENDED
+SIG_REBASED, SIG_UNRESOLVED, SIG_IDLE = abi.SIG_REBASED, abi.SIG_UNRESOLVED, abi.SIG_IDLE
+
+
+def reward_weights(per_step=0.0, kills=0.0, teams_kills=0.0, loot=0.0, damage=0.0, effect=0.0, hp=0.0, died=0.0, outcome=None):
+    """An abi.RewardWeights; outcome: {SF_* outcome code: weight} or a sequence of up to eight weights by code."""
+    w = abi.RewardWeights()
+    w.per_step, w.died = per_step, died
+    for j, x in enumerate((kills, teams_kills, loot, damage, effect, hp)):
+        w.w[j] = x
+    for code, x in (outcome.items() if isinstance(outcome, dict) else enumerate(outcome or ())):
+        w.outcome[code] = x
+    return w
+
+
+def decode_signals(vitals=None, delta=None):
+    """Host copies of sf_signals_step's outputs by field name: vitals int32 [..., 16] and / or delta int32 [..., 8] ->
+    {name: int32 [...]} (abi.VITALS_FIELDS, abi.DELTA_FIELDS; the delta's flag word under "flags" where only a delta is
+    given, else the vitals' — they are the same word), plus one bool array per flag bit: present, died, ended, rebased,
+    unresolved, idle."""
+    out = {}
+    if delta is not None:
+        d = np.asarray(delta, dtype=np.int32)
+        assert d.shape[-1] == abi.DELTA_WORDS
+        out.update({n: d[..., j] for j, n in enumerate(abi.DELTA_FIELDS)})
+    if vitals is not None:
+        v = np.asarray(vitals, dtype=np.int32)
+        assert v.shape[-1] == abi.VITALS_WORDS
+        out.update({n: v[..., j] for j, n in enumerate(abi.VITALS_FIELDS)})
+    if "flags" in out:
+        for bit, n in ((SIG_PRESENT, "present"), (SIG_DIED, "died"), (SIG_ENDED, "ended"), (SIG_REBASED, "rebased"),
+                       (SIG_UNRESOLVED, "unresolved"), (SIG_IDLE, "idle")):
+            out[n] = (out["flags"] & bit) != 0
+    return out
+
+
+class Signals:
+    """Per-step game signals of every (arena, agent) on the device (strikeforce.h sf_signals_*): step() is one
+    stream-ordered launch behind any step that writes, wherever a device address is given, the vitals (int32 [arenas]
+    [n_agents][16]), the delta since this object's previous step() (int32 [arenas][n_agents][8]) and the shaped reward
+    (float32 [arenas * n_agents], what the rollout buffer's d_reward takes; weights: an abi.RewardWeights, see
+    reward_weights()).  rebase_ptr: device uint8 [arenas][n_agents], non-zero where the caller restarted or loaded the
+    arena since the previous step() — reset_arenas(selected_ptr=)'s output as it is.  Pointers are device addresses (int)
+    or torch tensors.  close() before the environment's."""
+
+    def __init__(self, batch):
+        if not hasattr(batch.L, "sf_signals_create"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_signals_* entry points")
+        self.batch, self.L = batch, batch.L
+        self.h = C.c_void_p()
+        rc = self.L.sf_signals_create(batch.h, C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            raise StrikeForceError("sf_signals_create failed (%d): %s" % (rc, self.L.sf_last_error().decode()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.sf_signals_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _ptr(x):
+        return x.data_ptr() if hasattr(x, "data_ptr") else x
+
+    def step(self, vitals_ptr=None, delta_ptr=None, reward_ptr=None, rebase_ptr=None, weights=None):
+        io = abi.SignalsIO(self._ptr(vitals_ptr), self._ptr(delta_ptr), self._ptr(reward_ptr), self._ptr(rebase_ptr),
+                           weights if weights is not None else abi.RewardWeights())
+        self.batch._ck(self.L.sf_signals_step(self.batch.h, self.h, C.byref(io)), "sf_signals_step")
+
+    def status(self):
+        """(delta records that carried UNRESOLVED, records rebased by the detection alone) since the last call;
+        synchronises and clears."""
+        out = (C.c_int64 * abi.SIGNALS_STATUS_WORDS)()
+        self.batch._ck(self.L.sf_signals_status(self.h, C.byref(out)), "sf_signals_status")
+        return int(out[0]), int(out[1])
+
+
 class ArenaBatch:
     """A batch of independent arenas on one GPU.
 
@@ -269,6 +354,10 @@ class ArenaBatch:
     def snapshot(self, slots):
         """Device memory for `slots` arena states of this configuration (sf_snapshot_create): see Snapshot."""
         return Snapshot(self, slots)
+
+    def signals(self):
+        """Per-step vitals, deltas and a shaped reward on the device (sf_signals_create): see Signals."""
+        return Signals(self)
 
     def snapshot_slot_bytes(self):
         """(device bytes, blob bytes) one snapshot slot of this configuration takes: to budget before snapshot()."""
