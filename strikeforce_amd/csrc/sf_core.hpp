@@ -47,6 +47,18 @@ enum { LIM_PORTAL = 1000, LIM_BLOCK = 1100 };  // G:37
 // optimiser, a loaded field is not; with the call, loops were unswitched differently on p.mode and p.n_agents, and every
 // generic kernel's register allocation moved.)
 #define SF_SHAPE(f) (SH::FIXED ? SH::f(p) : p.f)
+// `x % 5 < n` for a generator draw (x < 1024), n = 2 or 3, without the remainder: the low ten bits of x * 205 are
+// 1024 (x % 5 / 5 + x / 5120) rounded down, which no x < 1024 carries past the next fifth.  Three scalar instructions, where
+// the remainder's multiply-subtract (Core::mod5) is selected as a vector mad with a vector compare behind it.  The fixed
+// instances use it (SF_MOD5_LT).
+constexpr uint32_t mod5_frac(uint32_t x) { return (x * 205u) & 1023u; }
+constexpr bool mod5_frac_exact() {
+  for (uint32_t x = 0; x < 1024u; ++x)
+    if ((x % 5u < 2u) != (mod5_frac(x) < 410u) || (x % 5u < 3u) != (mod5_frac(x) < 615u)) return false;
+  return true;
+}
+static_assert(mod5_frac_exact(), "x % 5 < 2 and x % 5 < 3 by the fraction's bits, for every x < 1024");
+#define SF_MOD5_LT(x, n) (SH::FIXED ? mod5_frac(x) < ((n) == 2u ? 410u : 615u) : mod5(x) < (n))
 template <class W, int NB, bool HBM_PLANE = false, bool BITMAPS = !HBM_PLANE, bool ZL = false, class SH = RuntimeShape>
 struct Core {
   using V = typename W::V;
@@ -88,6 +100,9 @@ struct Core {
     uint32_t la2_ok;
     // wave-uniform scalars  G:461
     int32_t frame, kills, tkills, loot, chests, steps, episodes, done, outcome, ended;
+    // fixed shapes only: frame % 30, % 40 << 8, % 50 << 16 (the spawn periods, G:1444-1449) in one word, kept beside `frame`
+    // by frame_phases() and frame_advance() so that no step divides.  A pure function of `frame`, like `la`: never stored
+    int32_t fph;
     uint32_t jomle;
     uint32_t tb_lo, tb_hi, sr_lo, sr_hi;
     uint32_t dirty;  // the LDS flag plane differs from HBM
@@ -497,10 +512,28 @@ struct Core {
     return q;  // ((f << 10) | r) << 10 | c == pos_pack(f, r, c)
   }
 
+  // The fixed shapes keep frame % {30, 40, 50} as counters (Arena::fph): set wherever `frame` is set, advanced with it,
+  // wrapped by a compare (`frame` counts up from 0 and is never negative).  The generic instances divide, as before.
+  static SF_DEV void frame_phases(Arena &S) {
+    if constexpr (SH::FIXED) S.fph = (S.frame % 30) | ((S.frame % 40) << 8) | ((S.frame % 50) << 16);
+  }
+  static SF_DEV void frame_advance(Arena &S) {
+    ++S.frame;
+    if constexpr (SH::FIXED) {
+      int32_t x = S.fph + 0x010101;
+      if ((x & 0xff) == 30) x -= 30;
+      if ((x & 0xff00) == (40 << 8)) x -= 40 << 8;
+      if ((x >> 16) == 50) x -= 50 << 16;
+      S.fph = x;
+    }
+  }
+  // (read as a conditional on a constant of the instance, like SF_SHAPE, so that the generic instances see the divisions
+  // themselves and not a call's result)
+#define SF_FRAME_MOD(n) (SH::FIXED ? ((S.fph >> (n == 30 ? 0 : n == 40 ? 8 : 16)) & 0xff) : S.frame % n)
   // spawn_chest / spawn_zombie_npc / spawn_human_npc G:532-572, at the loop top when frame % {30,40,50} <= 1
   // (G:1444-1449), in that order
   static SF_DEV void spawns(Arena &S, uint8_t *lds, const Params &p) {
-    const uint32_t due = (S.frame % 30 <= 1 ? 1u : 0u) | (S.frame % 40 <= 1 ? 2u : 0u) | (S.frame % 50 <= 1 ? 4u : 0u);
+    const uint32_t due = (SF_FRAME_MOD(30) <= 1 ? 1u : 0u) | (SF_FRAME_MOD(40) <= 1 ? 2u : 0u) | (SF_FRAME_MOD(50) <= 1 ? 4u : 0u);
     if (!due) return;
     SF_NOUNROLL for (int kind = 0; kind < 3; ++kind) {
       if (!((due >> kind) & 1u)) continue;
@@ -658,9 +691,24 @@ struct Core {
     while (movers) {
       const uint32_t z = (uint32_t)W::ctz64(movers);
       movers &= movers - 1ull;
-      if (mod5(draw(S, lds, p)) < 2u) continue;
+      if (SF_MOD5_LT(draw(S, lds, p), 2u)) continue;
       const uint32_t fb = W::readlane(freebits, z);
       const uint32_t zp = W::readlane(S.zpos, z);
+      if constexpr (SH::FIXED) {
+        // the two tries of the loop below written out, each one's verdict a value: the loop's `continue` and `break` cost
+        // about ten scalar instructions of flag keeping per try.  The ballot of a direction that is not free is asked for
+        // nothing (one compare) and ignored
+        uint32_t q = 0u;
+        bool go = false;
+        for (int i1 = 0; i1 < 2 && !go; ++i1) {  // (unrolled)
+          const uint32_t i2 = draw(S, lds, p) & 3u;
+          q = (zp & POS_MASK) + (uint32_t)(int32_t)(int16_t)(0xFFFFFC0000010400ull >> (i2 * 16u));
+          const uint64_t there = W::ballot((S.zpos & (ZF_ALIVE | POS_MASK)) == (ZF_ALIVE | q));
+          go = (((fb >> i2) & 1u) != 0u) & (there == 0ull);
+        }
+        if (go) W::setlane(S.zpos, z, (zp & ~POS_MASK) | q);
+        continue;
+      }
       SF_NOUNROLL for (int i1 = 0; i1 < 2; ++i1) {
         const uint32_t i2 = draw(S, lds, p) & 3u;
         if (!((fb >> i2) & 1u)) continue;
@@ -1433,10 +1481,10 @@ struct Core {
     constexpr uint64_t T_WEAPON = pack8("cvbnm,./", 8), T_MOVE = pack8("12awsdp", 7), T_MISC = pack8("+ufghj[]", 8);
     const uint32_t d1 = draw(S, lds, p);
     if (pick_weapon) return (uint32_t)(T_WEAPON >> ((d1 & 7u) * 8u)) & 255u;  // frame % 50 <= 1
-    if (mod5(d1) < 3u) return 'x';
+    if (SF_MOD5_LT(d1, 3u)) return 'x';
     const uint32_t d2 = draw(S, lds, p);
     const uint32_t d3 = draw(S, lds, p);
-    return mod5(d2) < 3u ? (uint32_t)(T_MOVE >> (mod7(d3) * 8u)) & 255u : (uint32_t)(T_MISC >> ((d3 & 7u) * 8u)) & 255u;
+    return SF_MOD5_LT(d2, 3u) ? (uint32_t)(T_MOVE >> (mod7(d3) * 8u)) & 255u : (uint32_t)(T_MISC >> ((d3 & 7u) * 8u)) & 255u;
   }
 
   // human_action G:965-1012.  S.hcmd holds this step's external commands on lanes < n_agents.
@@ -1488,7 +1536,7 @@ struct Core {
       const P ext = ((S.hfl & (HF_REMOTE | HF_CTRL)) != 0u) | (W::lane() == (uint32_t)SF_SHAPE(ind));
       S.hcmd = W::select(ext, S.hcmd, V((uint32_t)'+'));
       uint64_t m = alive & ~(1ull << SF_SHAPE(ind)) & W::ballot((S.hfl & (HF_RNPC | HF_REMOTE)) == HF_RNPC);
-      const bool pick_weapon = m && S.frame % 50 <= 1;  // the same for every NPC of this sweep
+      const bool pick_weapon = m && SF_FRAME_MOD(50) <= 1;  // the same for every NPC of this sweep
       while (m) {
         const uint32_t i = (uint32_t)W::ctz64(m);
         m &= m - 1ull;
@@ -1892,6 +1940,7 @@ struct Core {
   // `adopt`: the generator state for this seed was already warmed up in S.rl2 (see prewarm)
   static SF_DEV void reset_state(Arena &S, uint8_t *lds, const Params &p, uint64_t tb, uint64_t serial, bool adopt) {
     S.frame = S.kills = S.tkills = S.loot = S.chests = S.steps = 0;
+    frame_phases(S);
     S.done = 0, S.outcome = SF_RUNNING;
     S.tb_lo = (uint32_t)tb, S.tb_hi = (uint32_t)(tb >> 32), S.sr_lo = (uint32_t)serial, S.sr_hi = (uint32_t)(serial >> 32);
     S.hpos = V(POS_NONE), S.hfl = V(0u), S.hhp = V(0u), S.hst = V(0u), S.hmd = V(0u), S.hk = V(0u), S.hdm = V(0u);
@@ -1991,7 +2040,7 @@ struct Core {
       SF_STAMP(S, 5);
       hits(S, p);
       SF_STAMP(S, 6);
-      ++S.frame;  // updmap G:489-495 clears render-only bits
+      frame_advance(S);  // updmap G:489-495 clears render-only bits
       if (SF_SHAPE(auto_reset)) prewarm(S, lds, p, S.wrate);
       SF_STAMP(S, 4);
       const uint32_t j2 = S.jomle;
@@ -2006,6 +2055,15 @@ struct Core {
     }
     if (PHASE == 1) return;
     ++S.steps;
+    if constexpr (SH::FIXED && PHASE == 0) {
+      // the fixed instances' step loop (step_body_t) runs restart() itself, outside the path of a step that ends no game:
+      // reset_state's defaults are then no merge values of every step
+      const uint32_t j3 = S.jomle;
+      loop_top<LOG>(S, lds, p, a);
+      S.pd45 = ((S.jomle - j3) & 0xffffu) | (rest << 16);
+      SF_STAMP(S, 8);
+      return;
+    }
     // the loop top; when the episode ends and auto_reset is on, once more for the episode that begins
     SF_NOUNROLL for (int pass = 0; pass < 2; ++pass) {
       const uint32_t j3 = S.jomle;
@@ -2020,9 +2078,36 @@ struct Core {
       const int32_t ep = S.episodes;
       reset_state(S, lds, p, tb, sr, true);
       S.episodes = ep;
-      ++S.frame;  // G:1441
+      frame_advance(S);  // G:1441
     }
     SF_STAMP(S, 8);
+  }
+
+  // The fixed instances do not carry the arena's seeds over the step loop: the scalar block in HBM keeps the values of the
+  // launch's load() until store() writes it, the serial never changes, and the time base has advanced by `reseed` for every
+  // game begun since (restart() below, the only place that moves it).  Four registers less in the loop; read where a game
+  // begins and in store().
+  static SF_DEV void seeds_now(const Arena &S, const Params &p, int a, uint64_t &tb, uint64_t &sr) {
+    const int32_t *const sc = p.scal + (size_t)a * SC_WORDS;
+    const uint32_t begun = SF_SHAPE(auto_reset) ? (uint32_t)(S.episodes - W::uload_i32(sc + SC_EPISODES)) : 0u;
+    tb = (((uint64_t)(uint32_t)W::uload_i32(sc + SC_TB_HI) << 32) | (uint32_t)W::uload_i32(sc + SC_TB_LO)) +
+         (uint64_t)begun * (uint64_t)(uint32_t)p.reseed;
+    sr = ((uint64_t)(uint32_t)W::uload_i32(sc + SC_SR_HI) << 32) | (uint32_t)W::uload_i32(sc + SC_SR_LO);
+  }
+
+  // What step()'s loop-top loop does behind a loop top that ended the game (S.done): count the episode and, with auto_reset,
+  // set up the next one and run its first loop top.  The fixed instances call it from their step loop.
+  template <bool LOG>
+  static SF_DEV void restart(Arena &S, uint8_t *lds, const Params &p, int a) {
+    ++S.episodes;  // (Arena::ended follows from it: store())
+    if (!SF_SHAPE(auto_reset)) return;
+    uint64_t tb, sr;
+    seeds_now(S, p, a, tb, sr);  // (the game counted above included)
+    const int32_t ep = S.episodes;
+    reset_state(S, lds, p, tb, sr, true);
+    S.episodes = ep;
+    frame_advance(S);  // G:1441
+    loop_top<LOG>(S, lds, p, a);
   }
 
   // ------------------------------------------------------------------------------------------------
@@ -2095,6 +2180,7 @@ struct Core {
     }
     const V sc = W::gload((const uint32_t *)p.scal + (size_t)a * SC_WORDS, ln, W::ltu(ln, (uint32_t)SC_WORDS));
     S.frame = (int32_t)W::readlane(sc, SC_FRAME), S.kills = (int32_t)W::readlane(sc, SC_KILLS);
+    frame_phases(S);
     S.tkills = (int32_t)W::readlane(sc, SC_TKILLS), S.loot = (int32_t)W::readlane(sc, SC_LOOT);
     S.chests = (int32_t)W::readlane(sc, SC_CHESTS), S.jomle = W::readlane(sc, SC_JOMLE);
     S.steps = (int32_t)W::readlane(sc, SC_STEPS), S.episodes = (int32_t)W::readlane(sc, SC_EPISODES);
@@ -2173,9 +2259,19 @@ struct Core {
     W::setlane(sc, SC_CHESTS, (uint32_t)S.chests), W::setlane(sc, SC_JOMLE, S.jomle);
     W::setlane(sc, SC_STEPS, (uint32_t)S.steps), W::setlane(sc, SC_EPISODES, (uint32_t)S.episodes);
     W::setlane(sc, SC_DONE, (uint32_t)S.done), W::setlane(sc, SC_OUTCOME, (uint32_t)S.outcome);
-    W::setlane(sc, SC_ENDED, (uint32_t)S.ended);
-    W::setlane(sc, SC_TB_LO, S.tb_lo), W::setlane(sc, SC_TB_HI, S.tb_hi);
-    W::setlane(sc, SC_SR_LO, S.sr_lo), W::setlane(sc, SC_SR_HI, S.sr_hi);
+    if constexpr (SH::FIXED) {
+      // games that ended during this launch (sf_done with auto_reset), saturating: the count of games since load()
+      const uint32_t begun = (uint32_t)(S.episodes - W::uload_i32(p.scal + (size_t)a * SC_WORDS + SC_EPISODES));
+      W::setlane(sc, SC_ENDED, begun < 255u ? begun : 255u);
+      uint64_t tb, sr;
+      seeds_now(S, p, a, tb, sr);
+      W::setlane(sc, SC_TB_LO, (uint32_t)tb), W::setlane(sc, SC_TB_HI, (uint32_t)(tb >> 32));
+      W::setlane(sc, SC_SR_LO, (uint32_t)sr), W::setlane(sc, SC_SR_HI, (uint32_t)(sr >> 32));
+    } else {
+      W::setlane(sc, SC_ENDED, (uint32_t)S.ended);
+      W::setlane(sc, SC_TB_LO, S.tb_lo), W::setlane(sc, SC_TB_HI, S.tb_hi);
+      W::setlane(sc, SC_SR_LO, S.sr_lo), W::setlane(sc, SC_SR_HI, S.sr_hi);
+    }
     W::setlane(sc, SC_DRAWS, S.jomle - (18u + 1024u));  // _rand() calls since the episode's _srand: jomle counts them
     W::setlane(sc, SC_WARM, S.warm);
     W::setlane(sc, SC_PD01, S.pd01), W::setlane(sc, SC_PD23, S.pd23), W::setlane(sc, SC_PD45, S.pd45);
@@ -2229,7 +2325,7 @@ struct Core {
     S.rl2 = V(RL_ZERO), S.rseed2 = V(0u), S.warm = 0u, S.wrate = 1u;
     if constexpr (ZL) S.zwhi = (uint32_t)zw_for(SF_SHAPE(Z)), S.pwhi = (uint32_t)zw_for(p.P);  // store() writes the whole tables once: slots beyond zwn / pwn are zero in HBM from here on
     reset_state(S, lds, p, tb[a], serial[a], false);
-    ++S.frame;  // G:1441
+    frame_advance(S);  // G:1441
     loop_top(S, lds, p, a);
     store(S, lds, p, a);
   }
@@ -2266,7 +2362,7 @@ struct Core {
     S.rl2 = V(RL_ZERO), S.rseed2 = V(0u), S.warm = 0u, S.wrate = 1u;
     if constexpr (ZL) S.zwhi = (uint32_t)zw_for(SF_SHAPE(Z)), S.pwhi = (uint32_t)zw_for(p.P);  // the whole tables are written, as by reset_body: the game before may have had higher words in use
     reset_state(S, lds, p, tb, serial, false);
-    ++S.frame;  // G:1441
+    frame_advance(S);  // G:1441
     loop_top(S, lds, p, a);
     store(S, lds, p, a);
   }
@@ -2315,10 +2411,24 @@ struct Core {
     S.ended = 0;
     SF_STAMP_LOADED();
     SF_STAMP_BEGIN(S);
-    for (int s = 0; s < k; ++s) {
-      const uint8_t *c = cmds + ((size_t)s * (size_t)p.A + (size_t)a) * (size_t)SF_SHAPE(n_agents);
-      S.hcmd = W::select(ag, W::gload_u8(c, W::lane(), ag), V((uint32_t)'+'));
-      step<0, LOG>(S, lds, p, a);
+    if constexpr (SH::FIXED) {
+      // One command pointer that advances to its end, in place of a step number and its product with A: the pointer is the
+      // loop's count as well.  A game that ends takes the side branch to restart(); an arena that stays done (loaded so, or
+      // a new game that its first loop top ended) steps no further, as step() has it.
+      const size_t stride = (size_t)p.A * (size_t)SF_SHAPE(n_agents);
+      const uint8_t *c = cmds + (size_t)a * (size_t)SF_SHAPE(n_agents);
+      const uint8_t *const end = c + (size_t)(k > 0 ? k : 0) * stride;
+      for (; c != end && !S.done; c += stride) {
+        S.hcmd = W::select(ag, W::gload_u8(c, W::lane(), ag), V((uint32_t)'+'));
+        step<0, LOG>(S, lds, p, a);
+        if (S.done) restart<LOG>(S, lds, p, a);
+      }
+    } else {
+      for (int s = 0; s < k; ++s) {
+        const uint8_t *c = cmds + ((size_t)s * (size_t)p.A + (size_t)a) * (size_t)SF_SHAPE(n_agents);
+        S.hcmd = W::select(ag, W::gload_u8(c, W::lane(), ag), V((uint32_t)'+'));
+        step<0, LOG>(S, lds, p, a);
+      }
     }
     SF_STAMP_END(S, a);
     SF_STAMP_STEPPED();
@@ -2346,5 +2456,7 @@ struct Core {
   }
 };
 #undef SF_SHAPE
+#undef SF_FRAME_MOD
+#undef SF_MOD5_LT
 
 }  // namespace sf
