@@ -205,19 +205,12 @@ template <class R>
 struct has_ep_late<R, decltype((void)std::declval<R &>().launch_ep_late(std::declval<const Params &>(), true))> : std::true_type {};
 
 // whether a runtime has the fixed-shape step kernels (k_step_fixed; sf_types.hpp FixedShapes): it then carries the index
-// Env::create picked in `fixed_shape`.  The HIP runtime has them; the emulator's runtime of tests/emu runs generic instances
+// Env::create picked in `fixed_shape`.  Env::create is instantiated for every runtime, so a runtime without the member (one
+// that runs generic instances only) needs this to build at all; the HIP runtime and tests/emu's CpuRT both have it
 template <class R, class = void>
 struct has_fixed_shapes : std::false_type {};
 template <class R>
 struct has_fixed_shapes<R, decltype((void)std::declval<R &>().fixed_shape)> : std::true_type {};
-
-// whether a runtime has k_reset_sel (sf_reset_arenas).  The HIP runtime has it; the emulator's runtime of tests/emu does
-// not (tests/reset_sel_emu supplies one that has), and Env::reset_arenas answers SF_ERR_STATE there
-template <class R, class = void>
-struct has_reset_sel : std::false_type {};
-template <class R>
-struct has_reset_sel<R, decltype((void)std::declval<R &>().launch_reset_sel(std::declval<const Params &>(), 1, std::declval<const ResetSel &>()))>
-    : std::true_type {};
 
 template <class RT>
 struct Env {
@@ -439,14 +432,10 @@ struct Env {
     if (!sel->d_tb != !sel->d_serial) return fail(SF_ERR_ARG, "sf_reset_arenas: d_tb and d_serial must both be given or both be NULL");
     if (sel->d_mask && sel->mask_stride < 1) return fail(SF_ERR_ARG, "sf_reset_arenas: mask_stride must be at least 1");
     if (sel->max_steps < 0) return fail(SF_ERR_ARG, "sf_reset_arenas: max_steps must not be negative");
-    if constexpr (has_reset_sel<RT>::value) {
-      const ResetSel r = {sel->d_mask, sel->d_mask ? sel->mask_stride : 0, sel->done_too, sel->max_steps, sel->d_tb, sel->d_serial, sel->d_selected};
-      if (int rc = rt.launch_reset_sel(p, NB, r)) return rc;
-      steps_since_rank = 1 << 30;  // the populations the launch order was built from are gone
-      return SF_OK;
-    } else {
-      return fail(SF_ERR_STATE, "sf_reset_arenas: this runtime has no k_reset_sel");
-    }
+    const ResetSel r = {sel->d_mask, sel->d_mask ? sel->mask_stride : 0, sel->done_too, sel->max_steps, sel->d_tb, sel->d_serial, sel->d_selected};
+    if (int rc = rt.launch_reset_sel(p, NB, r)) return rc;
+    steps_since_rank = 1 << 30;  // the populations the launch order was built from are gone
+    return SF_OK;
   }
 
   int step_host(const uint8_t *cmd) {

@@ -3,7 +3,7 @@
 // the state buffers and the result latch the step kernels wrote.  Nothing of the environment is written.
 //
 // The per-agent body is a plain SF_HD function over pointers: k_signals (sf_api.hip) calls it with one lane per (arena,
-// agent), the tests' CPU runtime (tests/signals_emu) in a loop, and both compile this text.
+// agent), the tests' CPU runtime (tests/emu/sf_emu.cpp) in a loop, and both compile this text.
 //
 // A signals object keeps SIG_BASE_WORDS words per (arena, agent): what the previous call saw.  The arena's words (seed,
 // step count, episode count, done flag) are kept once per AGENT, not once per arena: the lanes of one arena may sit in

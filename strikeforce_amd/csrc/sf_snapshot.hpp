@@ -1,6 +1,6 @@
 // sf_snapshot.hpp — the device side of sf_snapshot_save / sf_snapshot_load: one copy body between the environment's state
 // buffers and a snapshot object's, written against the wave backend (W) like sf_core.hpp, so that k_snapshot (sf_api.hip)
-// and the tests' wave emulator (tests/snapshot_emu) run the same lines.
+// and the tests' wave emulator (tests/emu) run the same lines.
 //
 // One launch, grid (arenas, parts), one wavefront per workgroup.  Wavefront (a, part) reads slot_of_arena[a] — and, for a
 // load, the slot's valid word — once, through the wave-uniform load: the verdict is the same on every lane, and the

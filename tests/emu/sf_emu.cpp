@@ -1,7 +1,12 @@
-// sf_emu.cpp — TEST INFRASTRUCTURE: the device core (strikeforce_amd/csrc/sf_core.hpp) and the host API
-// (sf_host.hpp) compiled for the CPU against a 64-lane wave emulator.  Exports the C-ABI of
-// include/strikeforce.h with an `sfe_` prefix.  Loaded only by tests/ (CPU parity of the kernel logic
-// against the oracle, ASan/UBSan runs); never part of, or a fallback for, the product library.
+// sf_emu.cpp — TEST INFRASTRUCTURE: the device core (strikeforce_amd/csrc/sf_core.hpp, sf_snapshot.hpp, sf_signals.hpp)
+// and the host API (sf_host.hpp) compiled for the CPU against a 64-lane wave emulator.  Exports the C-ABI of
+// include/strikeforce.h with an `sfe_` prefix, plus observers of what the runtime launched.  Loaded only by tests/ (CPU
+// parity of the kernel logic against the oracle, ASan/UBSan runs); never part of, or a fallback for, the product library.
+//
+// CpuRT has every launch of the product's runtime whose kernel body lives in a shared header: each runs that body for
+// every arena (arena and part, agent) in turn, and device pointers are host memory.  Not emulated: k_ep_late (the split
+// step's episode records and the rings emptied by sf_reset on the device: sf_host.hpp has_ep_late; sf_reset empties the
+// rings with a host-side fill here), k_rank, the sparse / overflow observation kernels and sf_episodes' kernels (sf_api.hip).
 #include <stdlib.h>
 
 #include <vector>
@@ -11,13 +16,14 @@
 #include "../../strikeforce_amd/csrc/sf_core.hpp"
 #include "../../strikeforce_amd/csrc/sf_obs.hpp"
 #include "../../strikeforce_amd/csrc/sf_host.hpp"
+#include "../../strikeforce_amd/csrc/sf_snapshot.hpp"
 // clang-format on
 
 namespace sf {
 
 // the template arguments <NB, HP, BM, ZL> of the last launch of each kernel (sfe_last_variant): what the suite's own
 // restatement of the choice (tests/variant_cases.py expected_variant) is checked against
-enum { LV_RESET = 0, LV_STEP, LV_STEP_HALF, LV_KINDS };
+enum { LV_RESET = 0, LV_STEP, LV_STEP_HALF, LV_RESET_SEL, LV_KINDS };
 struct Variant {
   int32_t nb = 0, hp = 0, bm = 0, zl = 0;
 };
@@ -86,6 +92,13 @@ static void run_observe(const Params &p, float *out) {
 
 struct CpuRT {
   Variant last[LV_KINDS];
+  // the fixed-shape step path (k_step_fixed) is the product's, and opt-in here (sfe_fixed_shapes): a handle that has not
+  // opted in runs the generic instance for every configuration, so `last[LV_STEP]` and the op profile name one code path
+  int fixed_shape = -1;  // Env::create's choice (sf_types.hpp FixedShapes; -1 under SF_STEP_GENERIC=1 or off every shape)
+  bool use_fixed_shapes = false;
+  int last_step_shape = -1;  // what the last step launch ran: an index in FixedShapes, -1 a generic instance
+  int last_parts = 0;        // the grid's second dimension of the last snapshot launch
+  int signals_launches = 0;
   int init(int) { return SF_OK; }
   void shutdown() {}
   size_t max_lds() const { return 160 * 1024; }
@@ -101,7 +114,20 @@ struct CpuRT {
       return each_arena(p, last[LV_RESET], v, [&](uint8_t *lds, int a) { EmuCore<decltype(v)>::reset_body(lds, p, a, tb, serial); });
     });
   }
+  int launch_reset_sel(const Params &p, int NB, const ResetSel &sel) {
+    return with_variant(p, NB, [&](auto v) {
+      return each_arena(p, last[LV_RESET_SEL], v, [&](uint8_t *lds, int a) { EmuCore<decltype(v)>::reset_sel_body(lds, p, a, sel); });
+    });
+  }
   int launch_step(const Params &p, int NB, const uint8_t *cmds, int k) {
+    last_step_shape = use_fixed_shapes && !p.tab->ep_ring ? fixed_shape : -1;  // (the log's records are written by the generic LOG instance)
+    if (last_step_shape >= 0)  // (last[LV_STEP] keeps the last GENERIC launch: a fixed one shows in last_step_shape only)
+      return with_fixed_shape(last_step_shape, FixedShapes{}, SF_ERR_STATE, [&](auto sh) {
+        using SH = decltype(sh);
+        std::vector<uint8_t> lds(lds_bytes_for(p.cells_pad, p.lds_tab, p.Z, p.P));
+        for (int a = 0; a < p.A; ++a) Core<WaveEmu, SH::NB, false, true, false, SH>::template step_body_t<false>(lds.data(), p, a, cmds, k);
+        return (int)SF_OK;
+      });
     return with_variant(p, NB, [&](auto v) {
       return each_arena(p, last[LV_STEP], v, [&](uint8_t *lds, int a) { EmuCore<decltype(v)>::step_body(lds, p, a, cmds, k); });
     });
@@ -112,6 +138,26 @@ struct CpuRT {
     return with_variant(p, NB, [&](auto v) {
       return each_arena(p, last[LV_STEP_HALF], v, [&](uint8_t *lds, int a) { EmuCore<decltype(v)>::step_half_body(lds, p, a, cmds, phase); });
     });
+  }
+  int launch_replay_fetch(const Params &p, const Replay &r, int mode) {
+    for (int a = 0; a < p.A; ++a) Core<WaveEmu, 1>::replay_fetch(p, r, a, mode);
+    return SF_OK;
+  }
+  int launch_snapshot(const Snap &k, int parts, bool save) {
+    last_parts = parts;
+    for (int a = 0; a < k.A; ++a)
+      for (int part = 0; part < parts; ++part) {
+        if (save)
+          SnapCore<WaveEmu, true>::body(k, a, part);
+        else
+          SnapCore<WaveEmu, false>::body(k, a, part);
+      }
+    return SF_OK;
+  }
+  int launch_signals(const Signals &k) {
+    ++signals_launches;
+    for (int i = 0; i < k.A * k.n_agents; ++i) signals_agent(k, i);
+    return SF_OK;
   }
   int launch_agent_alive(const Params &p, uint8_t *out) {
     for (int i = 0; i < p.A * p.n_agents; ++i) {
@@ -141,6 +187,8 @@ struct CpuRT {
 struct sfe_env {
   sf::Env<sf::CpuRT> e;
 };
+typedef sf::Env<sf::CpuRT>::Snapshot sfe_snapshot;
+typedef sf::Env<sf::CpuRT>::SignalsObj sfe_signals;
 
 extern "C" {
 // op profile of the device source: out[0] = all vector ops, out[1 + ph] = vector ops in phase ph, out[1 + PH_COUNT + ph]
@@ -177,6 +225,7 @@ int sfe_destroy(sfe_env *env) {
   return SF_OK;
 }
 int sfe_reset(sfe_env *env, const uint64_t *tb, const uint64_t *serial) { return env->e.reset(tb, serial); }
+int sfe_reset_arenas(sfe_env *env, const sf_reset_sel *sel) { return env->e.reset_arenas(sel); }
 int sfe_step(sfe_env *env, const uint8_t *cmd) { return env->e.step_host(cmd); }
 int sfe_step_many(sfe_env *env, const uint8_t *cmds, int32_t k) { return env->e.step_device(cmds, k); }
 int sfe_step_begin(sfe_env *env) { return env->e.step_begin(); }
@@ -192,11 +241,56 @@ int sfe_dump_arena(sfe_env *env, int32_t a, sf_arena_hdr *hdr, sf_human_rec *hs,
   return env->e.dump_arena(a, hdr, hs, zs, bs, ps, cf, cd, cp);
 }
 const char *sfe_last_error(void) { return sf::last_error().c_str(); }
-// out[4] = NB, HP, BM, ZL of the last launch of kernel `kind` (0 reset, 1 step, 2 half step); all 0 before the first
+int sfe_episode_log(sfe_env *env, int32_t depth) { return env->e.episode_log(depth); }
+int sfe_episode_ring(sfe_env *env, int32_t *out) { return env->e.episode_ring_host(out); }
+int sfe_replay_load(sfe_env *env, const uint8_t *streams, const int64_t *offsets) { return env->e.replay_load(streams, offsets); }
+int sfe_replay_step(sfe_env *env) { return env->e.replay_step(); }
+int sfe_replay_status(sfe_env *env, int32_t *out) { return env->e.replay_status_host(out); }
+int sfe_replay_commands(sfe_env *env, uint8_t *out) { return env->e.replay_commands_device(out); }  // (one memory here)
+int sfe_snapshot_create(sfe_env *env, int32_t slots, sfe_snapshot **out) { return env->e.snapshot_create(slots, out); }
+int sfe_snapshot_destroy(sfe_snapshot *s) { return s ? s->owner->snapshot_destroy(s) : SF_OK; }
+int sfe_snapshot_slot_bytes(sfe_env *env, int64_t *d, int64_t *b) { return env->e.snapshot_slot_bytes(d, b); }
+int sfe_snapshot_save(sfe_env *env, sfe_snapshot *s, const int32_t *slot_of_arena) { return env->e.snapshot_copy(s, slot_of_arena, true); }
+int sfe_snapshot_load(sfe_env *env, sfe_snapshot *s, const int32_t *slot_of_arena) { return env->e.snapshot_copy(s, slot_of_arena, false); }
+int sfe_snapshot_status(sfe_snapshot *s, int32_t out[4]) { return s->owner->snapshot_status(s, out); }
+int sfe_snapshot_export(sfe_snapshot *s, int32_t slot, void *blob, int64_t bytes) { return s->owner->snapshot_export(s, slot, blob, bytes); }
+int sfe_snapshot_import(sfe_snapshot *s, int32_t slot, const void *blob, int64_t bytes) { return s->owner->snapshot_import(s, slot, blob, bytes); }
+int sfe_signals_create(sfe_env *env, sfe_signals **out) { return env->e.signals_create(out); }
+int sfe_signals_destroy(sfe_signals *s) { return s ? s->owner->signals_destroy(s) : SF_OK; }
+int sfe_signals_step(sfe_env *env, sfe_signals *s, const sf_signals_io *io) { return env->e.signals_step(s, io); }
+int sfe_signals_status(sfe_signals *s, int64_t out[4]) { return s ? s->owner->signals_status(s, out) : SF_ERR_ARG; }
+
+// Observers and switches of the emulated runtime (no counterpart in strikeforce.h).
+// out[4] = NB, HP, BM, ZL of the last launch of kernel `kind` (0 reset, 1 step, 2 half step, 3 reset_sel) by a generic
+// instance; all 0 before the first
 int sfe_last_variant(sfe_env *env, int32_t kind, int32_t *out) {
   if (kind < 0 || kind >= sf::LV_KINDS) return SF_ERR_ARG;
   const sf::Variant &v = env->e.rt.last[kind];
   out[0] = v.nb, out[1] = v.hp, out[2] = v.bm, out[3] = v.zl;
+  return SF_OK;
+}
+// whether this handle's step launches take the fixed-shape path where Env::create found a shape; a new handle does not
+int sfe_fixed_shapes(sfe_env *env, int32_t on) {
+  env->e.rt.use_fixed_shapes = on != 0;
+  return SF_OK;
+}
+// the fixed shape the last step launch ran (index in sf_types.hpp FixedShapes), -1: a generic instance
+int sfe_step_kernel(sfe_env *env) { return env->e.rt.last_step_shape; }
+// the grid's second dimension of the last snapshot launch (how many wavefronts shared one arena); 0 before the first
+int sfe_last_parts(sfe_env *env) { return env->e.rt.last_parts; }
+// launches of the signals kernel since create: a refused call must not add one
+int sfe_signals_launches(sfe_env *env) { return env->e.rt.signals_launches; }
+// raw words of one arena's scalar block, int32 [24]: what a dump does not show (SC_WARM, SC_ENDED, the pool word counts)
+int sfe_scal(sfe_env *env, int32_t a, int32_t *out) {
+  memcpy(out, env->e.p.scal + (size_t)a * sf::SC_WORDS, sf::SC_WORDS * sizeof(int32_t));
+  return SF_OK;
+}
+// what k_signals reads of the environment, raw: hum [HW_WORDS][A][H], scal [A][SC_WORDS], results [A][n_agents][8]
+int sfe_raw_state(sfe_env *env, uint32_t *hum, int32_t *scal, int32_t *results) {
+  const sf::Params &p = env->e.p;
+  memcpy(hum, p.hum, (size_t)sf::HW_WORDS * p.A * p.H * 4u);
+  memcpy(scal, p.scal, (size_t)p.A * sf::SC_WORDS * 4u);
+  memcpy(results, p.results, (size_t)p.A * p.n_agents * 8u * 4u);
   return SF_OK;
 }
 }

@@ -348,6 +348,37 @@ struct WaveEmu {
     for (int i = 0; i < 64; ++i)
       if ((pred.m >> i) & 1ull) base[idx.v[i]] = val.v[i];
   }
+  static void gstore_u8(uint8_t *base, const V &idx, const V &val, P pred) {
+    for (int i = 0; i < 64; ++i)
+      if ((pred.m >> i) & 1ull) base[idx.v[i]] = (uint8_t)val.v[i];
+  }
+  static void gstore_u16(uint16_t *base, const V &idx, const V &val, P pred) {
+    for (int i = 0; i < 64; ++i)
+      if ((pred.m >> i) & 1ull) base[idx.v[i]] = (uint16_t)val.v[i];
+  }
+  struct V4 {  // 16 bytes per lane (sf_snapshot.hpp)
+    uint8_t b[64][16];
+  };
+  static V4 gload16(const uint8_t *base, const V &off, P pred) {
+    V4 r;
+    for (int i = 0; i < 64; ++i)
+      if ((pred.m >> i) & 1ull)
+        memcpy(r.b[i], base + off.v[i], 16);
+      else
+        memset(r.b[i], 0, 16);
+    return r;
+  }
+  static void gstore16(uint8_t *base, const V &off, const V4 &val, P pred) {
+    for (int i = 0; i < 64; ++i)
+      if ((pred.m >> i) & 1ull) memcpy(base + off.v[i], val.b[i], 16);
+  }
+  static void ucount(uint32_t *counter) { ++*counter; }
+  static V rank_below(uint64_t bal) {  // v_mbcnt_lo / v_mbcnt_hi: the set bits of `bal` below the lane's own
+    EMU_OP();
+    V r;
+    for (int i = 0; i < 64; ++i) r.v[i] = (uint32_t)__builtin_popcountll(bal & ((1ull << i) - 1ull));
+    return r;
+  }
   static void copy_g2l(uint8_t *lds, const uint8_t *g, uint32_t n) { memcpy(lds, g, n); }
   // the copy in two halves (wave_gfx950.hpp: loads first, LDS stores later); here the source is read at the store
   template <int U>

@@ -1,4 +1,5 @@
-"""Loader for tests/emu/libsf_emu.so: the device core run on a CPU wave emulator.  Test infrastructure only."""
+"""Loader for tests/emu/libsf_emu.so: the device core run on a CPU wave emulator, with every `sfe_` entry point bound
+once.  Test infrastructure only."""
 import ctypes as C
 import os
 import subprocess
@@ -18,12 +19,27 @@ def lib(asan=False):
         # make is a no-op when the file __graft_entry__.build() made is up to date with its sources
         subprocess.check_call(["make", "-s", "-C", d, name])
         L = C.CDLL(os.path.join(d, name))
+        vp = C.c_void_p
         L.sfe_create.argtypes = [C.POINTER(abi.Config)]
-        L.sfe_create.restype = C.c_void_p
+        L.sfe_create.restype = vp
         abi.bind(L, "sfe_")
-        L.sfe_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
+        abi.bind_snapshot(L, "sfe_")
+        abi.bind_signals(L, "sfe_")
+        L.sfe_step_many.argtypes = [vp, C.c_char_p, C.c_int32]
         L.sfe_last_error.restype = C.c_char_p
-        L.sfe_last_variant.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
+        L.sfe_last_variant.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+        L.sfe_reset_arenas.argtypes = [vp, C.POINTER(abi.ResetSel)]
+        L.sfe_episode_log.argtypes = [vp, C.c_int32]
+        L.sfe_episode_ring.argtypes = [vp, vp]
+        L.sfe_replay_load.argtypes = [vp, vp, vp]
+        L.sfe_replay_step.argtypes = [vp]
+        L.sfe_replay_status.argtypes = [vp, vp]
+        L.sfe_replay_commands.argtypes = [vp, vp]
+        L.sfe_fixed_shapes.argtypes = [vp, C.c_int32]
+        for n in ("sfe_step_kernel", "sfe_last_parts", "sfe_signals_launches"):
+            getattr(L, n).argtypes = [vp]
+        L.sfe_scal.argtypes = [vp, C.c_int32, vp]
+        L.sfe_raw_state.argtypes = [vp] * 4
         _LIBS[name] = L
     return _LIBS[name]
 
@@ -101,11 +117,12 @@ class Emu:
     def dump(self, arena):
         return dump_with(self.L.sfe_dump_arena, self.h, self.cfg, arena)
 
-    KINDS = {"reset": 0, "step": 1, "step_half": 2}
+    KINDS = {"reset": 0, "step": 1, "step_half": 2, "reset_sel": 3}
 
     def last_variant(self, kind):
-        """(NB, HP, BM, ZL): the template arguments of the last launch of k_reset / k_step / k_step_half ("reset",
-        "step", "step_half"), as the device's launchers would pick them; (0, 0, 0, 0) before the first."""
+        """(NB, HP, BM, ZL): the template arguments of the last launch of k_reset / k_step / k_step_half / k_reset_sel
+        ("reset", "step", "step_half", "reset_sel"), as the device's launchers would pick them; (0, 0, 0, 0) before the
+        first."""
         out = (C.c_int32 * 4)()
         assert self.L.sfe_last_variant(self.h, self.KINDS[kind], out) == 0
         return tuple(out)

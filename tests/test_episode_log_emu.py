@@ -7,13 +7,9 @@ One-agent records on C3 and C2.  Records of 6 and of 16 agents on two cases of t
 schedule ends up to 13 games per arena and launch of 40 steps; and the first launch of every variant world, with the
 instance the host picks for it.
 
-The shim (tests/episode_log/sf_emu_episodes.cpp) is tests/emu's build plus sf_episode_log / sf_episode_ring.  k_ep_late
-(the split step's records, the rings emptied by sf_reset on the device) has no emulator counterpart:
+The emulator (tests/emu/sf_emu.cpp) exports sf_episode_log / sf_episode_ring over its runtime.  k_ep_late (the split
+step's records, the rings emptied by sf_reset on the device) has no emulator counterpart:
 tests/test_gpu_episode_log.py and tests/test_gpu_episode_log_edges.py cover it."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -22,35 +18,12 @@ import episode_log_cases as ec
 import variant_cases as vc
 from episode_log_ref import OracleEpisodes
 from oracle_lib import Oracle
-from strikeforce_amd import abi, config, env
+from strikeforce_amd import config, env
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SF_ERR_ARG = -1
 
 
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("episode_log") / "libsf_emu_episodes.so")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-shared",
-                           "-o", so, os.path.join(ROOT, "tests", "episode_log", "sf_emu_episodes.cpp")])
-    L = C.CDLL(so)
-    L.sfe_create.argtypes = [C.POINTER(abi.Config)]
-    L.sfe_create.restype = C.c_void_p
-    abi.bind(L, "sfe_")
-    L.sfe_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
-    L.sfe_last_error.restype = C.c_char_p
-    L.sfe_last_variant.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    L.sfe_episode_log.argtypes = [C.c_void_p, C.c_int32]
-    L.sfe_episode_ring.argtypes = [C.c_void_p, C.c_void_p]
-    return L
-
-
 class EmuLog(emu_lib.Emu):
-    def __init__(self, workload, L):  # (emu_lib.Emu's surface over the shim's library)
-        self.w, self.cfg, self.L = workload, workload.cfg, L
-        self.h = L.sfe_create(C.byref(self.cfg))
-        assert self.h, L.sfe_last_error().decode()
-
     def episode_log(self, depth):
         return self.L.sfe_episode_log(self.h, depth)
 
@@ -69,9 +42,9 @@ def workload(which, arenas):
 
 
 @pytest.mark.parametrize("which,arenas,steps,depth", [("C3", 6, 400, 8), ("C3", 4, 300, 2), ("C2", 8, 1200, 8)])
-def test_emulated_rings_equal_the_oracle_after_every_launch(shim, which, arenas, steps, depth):
+def test_emulated_rings_equal_the_oracle_after_every_launch(which, arenas, steps, depth):
     w = workload(which, arenas)
-    e = EmuLog(w, shim)
+    e = EmuLog(w)
     assert e.episode_log(depth) == 0
     tb, sr = w.seeds()
     e.reset(tb, sr)
@@ -109,13 +82,13 @@ def test_emulated_rings_equal_the_oracle_after_every_launch(shim, which, arenas,
 
 
 @pytest.mark.parametrize("case", ec.EMULATED, ids=lambda c: c.name)
-def test_emulated_rings_of_many_agents(shim, case):
+def test_emulated_rings_of_many_agents(case):
     """latch_results<true> under 6 agents (KITS: 56-word records) and under 16 (a variant_cases world: 136 words), five
     arenas under the schedule of tests/episode_log_cases.py, depth 4 with arenas that end 13, 5, 4, 3, 1 and 0 games in a
     launch of 40 steps; what the records carry is asserted in tests/test_episode_log_cases.py."""
     run = ec.oracle_run(case)
     w = case.workload()
-    e = EmuLog(w, shim)
+    e = EmuLog(w)
     assert e.episode_log(case.depth) == 0
     e.reset(*case.seeds())
     cmds = case.commands()
@@ -135,13 +108,13 @@ def test_emulated_rings_of_many_agents(shim, case):
 
 
 @pytest.mark.parametrize("case", ec.VARIANTS, ids=lambda c: c.name)
-def test_host_picks_the_expected_log_instance(shim, case):
+def test_host_picks_the_expected_log_instance(case):
     """All 15 variant worlds at the 5 arenas and depth 4 the device tests run them with: with the log on the host launches
     the instance variant_cases.expected_variant names (the emulated host's choice is the device host's: one dispatcher),
     and the rings behind the first launch equal the oracle's."""
     run = ec.oracle_run(case)
     w = case.workload()
-    e = EmuLog(w, shim)
+    e = EmuLog(w)
     assert e.episode_log(case.depth) == 0
     e.reset(*case.seeds())
     s0, n = case.launches()[0]
@@ -152,9 +125,9 @@ def test_host_picks_the_expected_log_instance(shim, case):
     e.close()
 
 
-def test_log_off_leaves_the_emulated_core_as_it_was(shim):
+def test_log_off_leaves_the_emulated_core_as_it_was():
     w = workload("C2", 4)
-    a, b = EmuLog(w, shim), emu_lib.Emu(w)
+    a, b = EmuLog(w), emu_lib.Emu(w)
     assert a.episode_log(4) == 0
     tb, sr = w.seeds()
     a.reset(tb, sr), b.reset(tb, sr)

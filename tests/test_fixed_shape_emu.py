@@ -1,64 +1,34 @@
 """The fixed-shape step kernel's body without a GPU: Core<WaveEmu, 1, false, true, false, FixedShape<C3>> (sf_core.hpp
 with BASELINE configs[2]'s configuration fields as compile-time constants, sf_types.hpp FixedShapes) on the wave emulator,
 selected by the product's own host code (sf_host.hpp Env::create), against the oracle and against the generic emulator
-instance, digest by digest.  The shim is tests/fixed_shape_emu/sf_emu_fixed.cpp: tests/emu's build plus a runtime that
-carries the fixed-shape launch path.
+instance, digest by digest.  The emulator's runtime (tests/emu/sf_emu.cpp) carries the fixed-shape launch path for a handle
+that opts in (sfe_fixed_shapes); every other handle runs generic instances.
 
 The world is C3's shape with a sturdy player who fires now and then, armed NPC humans, and a Timer game of 1 300 frames
 (timer_lim is not a fixed field), 720 steps.  A step is two frames and a zombie is spawned at most every 40 frames, so the
 cap of 24 zombies cannot be reached before step 480, whatever the seed (the oracle's own runs reach it between steps 480
 and 620); 300 steps would end with 15 zombies at most.  The game ends after 650 steps and restarts inside the run, so
 reset_state runs under the fixed shape with every pool populated before it."""
-import ctypes as C
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 import emu_lib
-from oracle_lib import Oracle, ROOT
+from oracle_lib import Oracle
 from strikeforce_amd import abi, config
 
 ARENAS, STEPS, TIMER_FRAMES = 4, 720, 1300
 C3_SHAPE, C2_SHAPE = 0, 1  # index of BASELINE configs[2] / configs[1] in sf_types.hpp FixedShapes
 
 
-@pytest.fixture(scope="module")
-def shim():
-    d = os.path.join(ROOT, "tests", "fixed_shape_emu")
-    # make is a no-op when the file __graft_entry__.build() made is up to date with its sources
-    subprocess.check_call(["make", "-s", "-C", d, "libsf_emu_fixed.so"])
-    L = C.CDLL(os.path.join(d, "libsf_emu_fixed.so"))
-    L.sfx_create.argtypes = [C.POINTER(abi.Config)]
-    L.sfx_create.restype = C.c_void_p
-    abi.bind(L, "sfx_")
-    L.sfx_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
-    L.sfx_last_error.restype = C.c_char_p
-    L.sfx_step_kernel.argtypes = [C.c_void_p]
-    return L
-
-
-class _AsEmu:
-    """The shim's sfx_ entry points under the sfe_ names emu_lib.Emu calls."""
-
-    def __init__(self, L):
-        self._L = L
-
-    def __getattr__(self, name):
-        return getattr(self._L, "sfx_" + name[4:] if name.startswith("sfe_") else name)
-
-
 class EmuFixed(emu_lib.Emu):
-    """emu_lib.Emu's surface over the shim's library, plus which step instance the last launch ran."""
+    """An emulator handle that has opted in to the fixed-shape step path, plus which step instance the last launch ran."""
 
-    def __init__(self, workload, L):
-        self.w, self.cfg, self.L = workload, workload.cfg, _AsEmu(L)
-        self.h = L.sfx_create(C.byref(self.cfg))
-        assert self.h, L.sfx_last_error().decode()
+    def __init__(self, workload):
+        emu_lib.Emu.__init__(self, workload)
+        assert self.L.sfe_fixed_shapes(self.h, 1) == 0
 
     def step_kernel(self):
-        return self.L.sfx_step_kernel(self.h)
+        return self.L.sfe_step_kernel(self.h)
 
 
 def world(arenas=ARENAS):
@@ -120,12 +90,12 @@ def test_the_oracle_run_fills_the_pools_and_restarts(oracle_run):
     assert (r["frames"][r["episodes"] >= 1] < TIMER_FRAMES).all()
 
 
-def test_fixed_shape_core_equals_oracle_and_generic_core(shim, oracle_run, monkeypatch):
+def test_fixed_shape_core_equals_oracle_and_generic_core(oracle_run, monkeypatch):
     w = world()
     monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
-    f = EmuFixed(w, shim)
+    f = EmuFixed(w)
     monkeypatch.setenv("SF_STEP_GENERIC", "1")
-    g = EmuFixed(world(), shim)
+    g = EmuFixed(world())
     monkeypatch.delenv("SF_STEP_GENERIC")
     tb, sr = w.seeds()
     f.reset(tb, sr), g.reset(tb, sr)
@@ -141,11 +111,11 @@ def test_fixed_shape_core_equals_oracle_and_generic_core(shim, oracle_run, monke
     f.close(), g.close()
 
 
-def test_long_launches_under_the_fixed_shape(shim, oracle_run, monkeypatch):
+def test_long_launches_under_the_fixed_shape(oracle_run, monkeypatch):
     """The step loop inside one launch (k = 7 and 100), as sf_step_device runs it."""
     monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
     w = world()
-    f = EmuFixed(w, shim)
+    f = EmuFixed(w)
     f.reset(*w.seeds())
     cmds = commands()
     s = 0
@@ -159,11 +129,11 @@ def test_long_launches_under_the_fixed_shape(shim, oracle_run, monkeypatch):
 
 
 @pytest.mark.parametrize("change", ["H 9", "Z 25", "64 x 63", "2 x 32 x 64", "two floors", "Solo", "Squad", "two agents", "level 2", "no auto_reset", "B 65", "P 65"])
-def test_any_other_configuration_selects_the_generic_instance(shim, change, monkeypatch):
+def test_any_other_configuration_selects_the_generic_instance(change, monkeypatch):
     """One fixed field off C3's shape (and P past the register pools): the host must not pick the fixed instance."""
     monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
     w = other_world(change, 2)
-    e = EmuFixed(w, shim)
+    e = EmuFixed(w)
     e.reset(*w.seeds())
     cmds, _ = config.bench_commands(2, w.cfg.n_agents, 3)
     for s in range(3):
@@ -172,15 +142,15 @@ def test_any_other_configuration_selects_the_generic_instance(shim, change, monk
     e.close()
 
 
-def test_c2_shape_core_equals_oracle_and_generic_core(shim, monkeypatch):
+def test_c2_shape_core_equals_oracle_and_generic_core(monkeypatch):
     """The second shape of the table, BASELINE configs[1] (Solo, 1 player + 16 zombies) under the random-action agent, 400
     steps: the oracle's own run fills the zombie pool and ends a game in one of the four arenas."""
     A, steps = 4, 400
     w = config.baseline_workload("C2", arenas=A)
     monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
-    f = EmuFixed(w, shim)
+    f = EmuFixed(w)
     monkeypatch.setenv("SF_STEP_GENERIC", "1")
-    g = EmuFixed(config.baseline_workload("C2", arenas=A), shim)
+    g = EmuFixed(config.baseline_workload("C2", arenas=A))
     monkeypatch.delenv("SF_STEP_GENERIC")
     o = Oracle(config.baseline_workload("C2", arenas=A))
     tb, sr = w.seeds()

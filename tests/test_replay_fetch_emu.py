@@ -1,94 +1,44 @@
 """The device form of the replay (sf_replay_load / sf_replay_step) without a GPU: sf_core.hpp Core::replay_fetch — the
 body of the gfx950 kernel k_replay_fetch — on the wave emulator, between the emulated halves of the step, through the
-host code of the product (sf_host.hpp Env::replay_load / replay_step).  The shim (tests/replay_emu/sf_emu_replay.cpp) is
-tests/emu's build plus the two wave operations and the launcher the fetch adds.  Checked against the reference client's
-own per-iteration digests (tests/golden/online_samples.json) and against the host form (replay.replay_lines)."""
+host code of the product (sf_host.hpp Env::replay_load / replay_step); the emulator and its runtime (tests/emu) have the
+two wave operations and the launcher the fetch adds.  Checked against the reference client's own per-iteration digests
+(tests/golden/online_samples.json) and against the host form (replay.replay_lines)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import emu_lib
 import online_cases as oc
-from oracle_lib import Oracle, ROOT, diff_dumps
+from oracle_lib import Oracle, diff_dumps
 from strikeforce_amd import abi, replay
 
 
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("replay_emu") / "libsf_emu_replay.so")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-shared",
-                           "-o", so, os.path.join(ROOT, "tests", "replay_emu", "sf_emu_replay.cpp")])
-    L = C.CDLL(so)
-    L.sfr_create.argtypes = [C.POINTER(abi.Config)]
-    L.sfr_create.restype = C.c_void_p
-    abi.bind(L, "sfr_")
-    L.sfr_last_error.restype = C.c_char_p
-    L.sfr_replay_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    for n in ("sfr_replay_step", "sfr_replay_status", "sfr_replay_commands"):
-        getattr(L, n).argtypes = [C.c_void_p] + ([C.c_void_p] if n != "sfr_replay_step" else [])
-    return L
-
-
 class EmuReplay(emu_lib.Emu):
-    """emu_lib.Emu's surface over the shim's library, plus ArenaBatch's replay_* calls."""
-
-    def __init__(self, workload, L):
-        self.w, self.cfg, self.L = workload, workload.cfg, L
-        self.h = L.sfr_create(C.byref(self.cfg))
-        assert self.h, L.sfr_last_error().decode()
-
-    def close(self):
-        if self.h:
-            self.L.sfr_destroy(self.h)
-            self.h = None
-
-    def reset(self, tb, serial):
-        assert self.L.sfr_reset(self.h, tb, serial) == 0
-
-    def done(self):
-        out = np.zeros(self.cfg.arenas, dtype=np.uint8)
-        assert self.L.sfr_done(self.h, out.ctypes.data_as(C.POINTER(C.c_uint8))) == 0
-        return out
-
-    def digest(self):
-        out = np.zeros(self.cfg.arenas, dtype=np.uint64)
-        assert self.L.sfr_state_digest(self.h, out.ctypes.data_as(C.POINTER(C.c_uint64))) == 0
-        return out
-
-    def dump(self, arena):
-        from oracle_lib import dump_with
-        return dump_with(self.L.sfr_dump_arena, self.h, self.cfg, arena)
-
-    def results(self):
-        out = np.zeros((self.cfg.arenas, self.cfg.n_agents, 8), dtype=np.int32)
-        assert self.L.sfr_results(self.h, out.ctypes.data_as(C.POINTER(C.c_int32))) == 0
-        return out
+    """emu_lib.Emu plus ArenaBatch's replay_* calls."""
 
     def replay_load(self, streams):
         if streams is None:
-            return self.L.sfr_replay_load(self.h, None, None)
+            return self.L.sfe_replay_load(self.h, None, None)
         rows = [getattr(s, "commands", s).encode("ascii") for s in streams]
         off = np.zeros(len(rows) + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(r) for r in rows])
         flat = np.frombuffer(b"".join(rows) or b"\0", dtype=np.uint8)
-        rc = self.L.sfr_replay_load(self.h, flat.ctypes.data, off.ctypes.data)
-        assert rc == 0, self.L.sfr_last_error().decode()
+        rc = self.L.sfe_replay_load(self.h, flat.ctypes.data, off.ctypes.data)
+        assert rc == 0, self.L.sfe_last_error().decode()
 
     def replay_step(self):
-        rc = self.L.sfr_replay_step(self.h)
-        assert rc == 0, self.L.sfr_last_error().decode()
+        rc = self.L.sfe_replay_step(self.h)
+        assert rc == 0, self.L.sfe_last_error().decode()
 
     def replay_status(self):
         out = np.zeros((self.cfg.arenas, 4), dtype=np.int32)
-        assert self.L.sfr_replay_status(self.h, out.ctypes.data) == 0
+        assert self.L.sfe_replay_status(self.h, out.ctypes.data) == 0
         return out
 
     def replay_commands(self):
         out = np.zeros((self.cfg.arenas, self.cfg.n_agents), dtype=np.uint8)
-        assert self.L.sfr_replay_commands(self.h, out.ctypes.data) == 0
+        assert self.L.sfe_replay_commands(self.h, out.ctypes.data) == 0
         return out
 
 
@@ -99,9 +49,9 @@ def _expected_lines(s, f):
 
 
 @pytest.mark.parametrize("name", oc.NAMES)
-def test_the_fetch_body_replays_the_reference_clients_matches(shim, name):
+def test_the_fetch_body_replays_the_reference_clients_matches(name):
     s, f = oc.load(name)
-    sim = EmuReplay(oc.workload(s, f), shim)
+    sim = EmuReplay(oc.workload(s, f))
     sim.reset((C.c_uint64 * 1)(s.tb), (C.c_uint64 * 1)(s.serial))
     sim.replay_load([s])
     lines = _expected_lines(s, f)
@@ -126,13 +76,13 @@ def test_the_fetch_body_replays_the_reference_clients_matches(shim, name):
     assert diff_dumps(b, sim.dump(0).as_dict()) is None
 
 
-def test_a_batch_on_the_emulator_each_arena_stops_at_its_own_length(shim, tmp_path):
+def test_a_batch_on_the_emulator_each_arena_stops_at_its_own_length(tmp_path):
     """24 matches played here on the oracle (a rival quits in every sixth, every sixth is cut in mid-iteration), one per
     arena: state, cursor, iterations and the final digest of every arena equal the host form's on the oracle."""
     made = oc.batch_samples(tmp_path, n=24)
     assert {k for _, k, _ in made} == {"plain", "quit", "cut"}
     samples = [s for s, _, _ in made]
-    sim = EmuReplay(oc.workload(samples[0], oc.BATCH, arenas=len(samples)), shim)
+    sim = EmuReplay(oc.workload(samples[0], oc.BATCH, arenas=len(samples)))
     st = replay.replay_batch(samples, sim)
     digests = sim.digest()
     for a, (s, kind, iters) in enumerate(made):
@@ -143,10 +93,10 @@ def test_a_batch_on_the_emulator_each_arena_stops_at_its_own_length(shim, tmp_pa
         assert int(digests[a]) == oc.digest_of_dump(o.dump(0), o.cfg, done=1, outcome=abi.SAMPLE_END), (a, kind)
 
 
-def test_a_game_that_check_end_ends_leaves_its_stream_unread(shim):
+def test_a_game_that_check_end_ends_leaves_its_stream_unread():
     s, f = oc.load("online_plain")
     s.commands = s.commands[:30] + "_" + s.commands[31:]  # `ind` gives up in iteration 11
-    sim = EmuReplay(oc.workload(s, f), shim)
+    sim = EmuReplay(oc.workload(s, f))
     st = replay.replay_batch([s], sim)
     o = Oracle(oc.workload(s, f))
     end = replay.replay_lines(s, o)
@@ -155,12 +105,12 @@ def test_a_game_that_check_end_ends_leaves_its_stream_unread(shim):
     assert sim.dump(0).hdr.episodes == 1 and sim.results()[0].any()
 
 
-def test_loading_needs_a_single_episode_env_and_a_load(shim):
+def test_loading_needs_a_single_episode_env_and_a_load():
     s, f = oc.load("online_plain")
     w = oc.workload(s, f)
     w.cfg.auto_reset = 1
-    sim = EmuReplay(w, shim)
+    sim = EmuReplay(w)
     rows = s.commands.encode()
     off = np.array([0, len(rows)], dtype=np.int64)
-    assert shim.sfr_replay_load(sim.h, rows, off.ctypes.data) == -4 and b"auto_reset" in shim.sfr_last_error()
-    assert shim.sfr_replay_step(sim.h) == -4 and b"no command streams loaded" in shim.sfr_last_error()
+    assert sim.L.sfe_replay_load(sim.h, rows, off.ctypes.data) == -4 and b"auto_reset" in sim.L.sfe_last_error()
+    assert sim.L.sfe_replay_step(sim.h) == -4 and b"no command streams loaded" in sim.L.sfe_last_error()

@@ -4,12 +4,10 @@ few calls interleaved with steps — the chosen arenas a fresh reset with the ep
 for an LDS-plane, an HBM-plane and a large-pool instance and for every game mode; the host's refusals; and the
 auto_reset = 0 + done_too loop against an auto_reset = 1 twin.
 
-The shim (tests/reset_sel_emu/sf_emu_reset_sel.cpp) is tests/emu's build with a runtime that has the launch; here the
-pointers of sf_reset_sel are host memory.  The pointer checks of the HIP runtime, stream order and the composition with the
-policy library are covered on the device (tests/test_gpu_reset_sel.py)."""
+The emulator's runtime (tests/emu/sf_emu.cpp) has the launch; here the pointers of sf_reset_sel are host memory.  The
+pointer checks of the HIP runtime, stream order and the composition with the policy library are covered on the device
+(tests/test_gpu_reset_sel.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -19,47 +17,14 @@ import reset_sel_cases as rc
 from reset_sel_ref import ResetSelRef, seed_stride
 from strikeforce_amd import abi, config
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SF_ERR_ARG, SF_ERR_STATE = -1, -4
 
 
-class _Prefix:
-    """The shim's `sfs_` entry points under the `sfe_` names emu_lib.Emu calls."""
-
-    def __init__(self, L):
-        self._L = L
-
-    def __getattr__(self, n):
-        return getattr(self._L, "sfs_" + n[4:] if n.startswith("sfe_") else n)
-
-
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("reset_sel") / "libsf_emu_reset_sel.so")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-shared",
-                           "-o", so, os.path.join(ROOT, "tests", "reset_sel_emu", "sf_emu_reset_sel.cpp")])
-    L = C.CDLL(so)
-    L.sfs_create.argtypes = [C.POINTER(abi.Config)]
-    L.sfs_create.restype = C.c_void_p
-    abi.bind(L, "sfs_")
-    L.sfs_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
-    L.sfs_last_error.restype = C.c_char_p
-    L.sfs_last_variant.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
-    L.sfs_reset_arenas.argtypes = [C.c_void_p, C.POINTER(abi.ResetSel)]
-    L.sfs_replay_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    return _Prefix(L)
-
-
 class EmuSel(emu_lib.Emu):
-    def __init__(self, workload, L):  # (emu_lib.Emu's surface over the shim's library)
-        self.w, self.cfg, self.L = workload, workload.cfg, L
-        self.h = L.sfe_create(C.byref(self.cfg))
-        assert self.h, L.sfe_last_error().decode()
-
     def reset_arenas_rc(self, mask=None, mask_stride=1, done=False, max_steps=0, tb=None, serial=None, selected=None):
         ptr = lambda x: None if x is None else x.ctypes.data
         sel = abi.ResetSel(ptr(mask), mask_stride, 1 if done else 0, max_steps, ptr(tb), ptr(serial), ptr(selected))
-        return self.L.sfs_reset_arenas(self.h, C.byref(sel))
+        return self.L.sfe_reset_arenas(self.h, C.byref(sel))
 
     def reset_arenas(self, **kw):
         assert self.reset_arenas_rc(**kw) == 0, self.L.sfe_last_error().decode()
@@ -111,12 +76,12 @@ def steps_both(e, ref, cmds, what, dumps_at_end=True):
 
 
 @pytest.mark.parametrize("name", ["lds-nb1", "hbm-bm", "hbm", "zl", "solo", "kits", "b8", "lds-nb2"])
-def test_emulated_restart_equals_the_restatement(shim, name):
+def test_emulated_restart_equals_the_restatement(name):
     A = 2 if name == "zl" else 3
     w = rc.workload(name, A)
     n = w.cfg.n_agents
     tb, sr = w.seeds()
-    e, ref = EmuSel(w, shim), ResetSelRef(w, tb, sr)
+    e, ref = EmuSel(w), ResetSelRef(w, tb, sr)
     e.reset(tb, sr)
     lead = rc.ZL_STEPS if name == "zl" else 30
     cmds = rc.commands(name, A, n, lead + 60)
@@ -130,7 +95,7 @@ def test_emulated_restart_equals_the_restatement(shim, name):
     compare_all(e, ref, "before the first call")
     sel = call_both(e, ref, "alternating, seeds given", mask=rc.selection("alternating", A), seeds_base=5000)
     assert sel.tolist() == [bool((a + 1) % 2) for a in range(A)]
-    assert e.last_variant("reset") == rc.VARIANT[name]
+    assert e.last_variant("reset_sel") == rc.VARIANT[name]
     steps_both(e, ref, cmds[lead:lead + 20], "after call 1")
     call_both(e, ref, "last, by sf_done_device's stride, the next seed", mask=rc.selection("last", A), stride=n)
     steps_both(e, ref, cmds[lead + 20:lead + 40], "after call 2")
@@ -143,13 +108,13 @@ def test_emulated_restart_equals_the_restatement(shim, name):
     e.close(), ref.close()
 
 
-def test_done_too_restarts_what_quit_and_keeps_ordinal_and_latch(shim):
+def test_done_too_restarts_what_quit_and_keeps_ordinal_and_latch():
     """The reference's own quit command ends a game as an episode; done_too then restarts it: the ordinal goes on counting
     and the result latch keeps the record of the game that ended."""
     A = 4
     w = rc.workload("solo", A)
     tb, sr = w.seeds()
-    e, ref = EmuSel(w, shim), ResetSelRef(w, tb, sr)
+    e, ref = EmuSel(w), ResetSelRef(w, tb, sr)
     e.reset(tb, sr)
     cmds = rc.commands("solo", A, 1, 30)
     cmds[9, 1::2] = ord("_")
@@ -168,11 +133,11 @@ def test_done_too_restarts_what_quit_and_keeps_ordinal_and_latch(shim):
     e.close(), ref.close()
 
 
-def test_done_too_after_every_step_is_auto_reset(shim):
+def test_done_too_after_every_step_is_auto_reset():
     A, steps = 8, 500  # configs[1]: games end at steps 146, 206, 433 and 469 (tests/test_reset_sel_ref.py)
     w1, w0 = config.baseline_workload("C2", arenas=A, auto_reset=1), config.baseline_workload("C2", arenas=A, auto_reset=0)
     tb, sr = w1.seeds()
-    auto, e = emu_lib.Emu(w1), EmuSel(w0, shim)
+    auto, e = emu_lib.Emu(w1), EmuSel(w0)
     auto.reset(tb, sr), e.reset(tb, sr)
     cmds, _ = config.bench_commands(A, 1, steps)
     restarts = 0
@@ -191,13 +156,13 @@ def test_done_too_after_every_step_is_auto_reset(shim):
     auto.close(), e.close()
 
 
-def test_with_auto_reset_the_episode_after_a_restart_takes_the_next_seed(shim):
+def test_with_auto_reset_the_episode_after_a_restart_takes_the_next_seed():
     A = 3
     w = rc.workload("lds-nb1", A, auto_reset=1)
     w.cfg.timer_frames_per_level = 30  # every Timer game ends at frame 31
     w.cfg.reseed_stride = 1000
     tb, sr = w.seeds()
-    e, ref = EmuSel(w, shim), ResetSelRef(w, tb, sr)
+    e, ref = EmuSel(w), ResetSelRef(w, tb, sr)
     e.reset(tb, sr)
     cmds = rc.commands("lds-nb1", A, 1, 50)
     steps_both(e, ref, cmds[:10], "lead")
@@ -212,9 +177,9 @@ def test_with_auto_reset_the_episode_after_a_restart_takes_the_next_seed(shim):
     e.close(), ref.close()
 
 
-def test_refusals(shim):
+def test_refusals():
     w = rc.workload("solo", 2)
-    e = EmuSel(w, shim)
+    e = EmuSel(w)
     tb8, mask = np.zeros(2, dtype=np.uint64), np.ones(2, dtype=np.uint8)
     assert e.reset_arenas_rc(done=True) == SF_ERR_STATE  # before the first sf_reset
     e.reset(*w.seeds())
@@ -223,16 +188,16 @@ def test_refusals(shim):
     assert e.reset_arenas_rc(mask=mask, mask_stride=0) == SF_ERR_ARG and e.reset_arenas_rc(mask=mask, mask_stride=-1) == SF_ERR_ARG
     assert e.reset_arenas_rc(mask_stride=0) == 0  # (no mask: the stride is not looked at)
     assert e.reset_arenas_rc(max_steps=-1) == SF_ERR_ARG
-    assert e.L.sfs_reset_arenas(e.h, None) == SF_ERR_ARG
+    assert e.L.sfe_reset_arenas(e.h, None) == SF_ERR_ARG
     e.step_begin()
     assert e.reset_arenas_rc(done=True) == SF_ERR_STATE
     e.step_end(np.full((2, 1), ord("+"), dtype=np.uint8))
     after = e.digest()
     stream = np.frombuffer(b"++", dtype=np.uint8)
     off = np.array([0, 1, 2], dtype=np.int64)
-    assert e.L.sfs_replay_load(e.h, stream.ctypes.data, off.ctypes.data) == 0
+    assert e.L.sfe_replay_load(e.h, stream.ctypes.data, off.ctypes.data) == 0
     assert e.reset_arenas_rc(mask=mask) == SF_ERR_STATE  # while a replay is loaded
-    assert e.L.sfs_replay_load(e.h, None, None) == 0
+    assert e.L.sfe_replay_load(e.h, None, None) == 0
     assert (e.digest() == after).all() and (after != before).any()
     assert e.reset_arenas_rc(mask=mask) == 0
     e.close()

@@ -4,12 +4,9 @@ dumps, done flags and digests of EVERY arena after each call, for an LDS-plane, 
 every game mode; the large pools in both directions (a small state into an arena whose tables were in use past word 0, and
 back); bad indices; the blob through the host code; the host's refusals.
 
-The shim (tests/snapshot_emu/sf_emu_snapshot.cpp) is tests/emu's build with a runtime that has the launch; here the index
-arrays are host memory.  The pointer checks of the HIP runtime and stream order are covered on the device
-(tests/test_gpu_snapshot.py)."""
+The emulator's runtime (tests/emu/sf_emu.cpp) has the launch; here the index arrays are host memory.  The pointer checks
+of the HIP runtime and stream order are covered on the device (tests/test_gpu_snapshot.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -20,98 +17,64 @@ import snapshot_cases as sc
 from snapshot_ref import SnapshotRef
 from strikeforce_amd import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SF_ERR_ARG, SF_ERR_STATE = -1, -4
-
-
-class _Prefix:
-    """The shim's `sfn_` entry points under the `sfe_` names emu_lib.Emu calls."""
-
-    def __init__(self, L):
-        self._L = L
-
-    def __getattr__(self, n):
-        return getattr(self._L, "sfn_" + n[4:] if n.startswith("sfe_") else n)
-
-
-@pytest.fixture(scope="module")
-def shim(tmp_path_factory):
-    so = str(tmp_path_factory.mktemp("snapshot") / "libsf_emu_snapshot.so")
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wno-unknown-pragmas", "-fPIC", "-shared",
-                           "-o", so, os.path.join(ROOT, "tests", "snapshot_emu", "sf_emu_snapshot.cpp")])
-    L = C.CDLL(so)
-    L.sfn_create.argtypes = [C.POINTER(abi.Config)]
-    L.sfn_create.restype = C.c_void_p
-    abi.bind(L, "sfn_")
-    abi.bind_snapshot(L, "sfn_")
-    L.sfn_step_many.argtypes = [C.c_void_p, C.c_char_p, C.c_int32]
-    L.sfn_last_error.restype = C.c_char_p
-    L.sfn_replay_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.sfn_last_parts.argtypes = [C.c_void_p]
-    L.sfn_scal.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-    return _Prefix(L)
 
 
 class EmuSnapshot:
     def __init__(self, e, slots):
         self.e, self.L, self.slots = e, e.L, slots
         self.h = C.c_void_p()
-        assert self.L.sfn_snapshot_create(e.h, slots, C.byref(self.h)) == 0, self.L.sfn_last_error().decode()
+        assert self.L.sfe_snapshot_create(e.h, slots, C.byref(self.h)) == 0, self.L.sfe_last_error().decode()
         d, b = C.c_int64(), C.c_int64()
-        assert self.L.sfn_snapshot_slot_bytes(e.h, C.byref(d), C.byref(b)) == 0
+        assert self.L.sfe_snapshot_slot_bytes(e.h, C.byref(d), C.byref(b)) == 0
         self.device_bytes, self.blob_bytes = d.value, b.value
 
     def save_rc(self, slot_of_arena):
-        return self.L.sfn_snapshot_save(self.e.h, self.h, None if slot_of_arena is None else slot_of_arena.ctypes.data)
+        return self.L.sfe_snapshot_save(self.e.h, self.h, None if slot_of_arena is None else slot_of_arena.ctypes.data)
 
     def load_rc(self, slot_of_arena):
-        return self.L.sfn_snapshot_load(self.e.h, self.h, None if slot_of_arena is None else slot_of_arena.ctypes.data)
+        return self.L.sfe_snapshot_load(self.e.h, self.h, None if slot_of_arena is None else slot_of_arena.ctypes.data)
 
     def save(self, slot_of_arena):
-        assert self.save_rc(slot_of_arena) == 0, self.L.sfn_last_error().decode()
+        assert self.save_rc(slot_of_arena) == 0, self.L.sfe_last_error().decode()
 
     def load(self, slot_of_arena):
-        assert self.load_rc(slot_of_arena) == 0, self.L.sfn_last_error().decode()
+        assert self.load_rc(slot_of_arena) == 0, self.L.sfe_last_error().decode()
 
     def status(self):
         out = (C.c_int32 * 4)()
-        assert self.L.sfn_snapshot_status(self.h, C.byref(out)) == 0
+        assert self.L.sfe_snapshot_status(self.h, C.byref(out)) == 0
         assert out[2] == 0 and out[3] == 0
         return out[0], out[1]
 
     def export_rc(self, slot, size=None):
         buf = C.create_string_buffer(self.blob_bytes)
-        return self.L.sfn_snapshot_export(self.h, slot, C.cast(buf, C.c_void_p), self.blob_bytes if size is None else size), buf.raw
+        return self.L.sfe_snapshot_export(self.h, slot, C.cast(buf, C.c_void_p), self.blob_bytes if size is None else size), buf.raw
 
     def export(self, slot):
         rc_, blob = self.export_rc(slot)
-        assert rc_ == 0, self.L.sfn_last_error().decode()
+        assert rc_ == 0, self.L.sfe_last_error().decode()
         return blob
 
     def import_rc(self, slot, blob):
-        return self.L.sfn_snapshot_import(self.h, slot, C.cast(C.c_char_p(blob), C.c_void_p), len(blob))
+        return self.L.sfe_snapshot_import(self.h, slot, C.cast(C.c_char_p(blob), C.c_void_p), len(blob))
 
     def import_(self, slot, blob):
-        assert self.import_rc(slot, blob) == 0, self.L.sfn_last_error().decode()
+        assert self.import_rc(slot, blob) == 0, self.L.sfe_last_error().decode()
 
     def close(self):
         if self.h:
-            self.L.sfn_snapshot_destroy(self.h)
+            self.L.sfe_snapshot_destroy(self.h)
             self.h = None
 
 
 class EmuSnap(emu_lib.Emu):
-    def __init__(self, workload, L):  # (emu_lib.Emu's surface over the shim's library)
-        self.w, self.cfg, self.L = workload, workload.cfg, L
-        self.h = L.sfe_create(C.byref(self.cfg))
-        assert self.h, L.sfe_last_error().decode()
-
     def snapshot(self, slots):
         return EmuSnapshot(self, slots)
 
     def scal(self, a):
         out = np.zeros(24, dtype=np.int32)
-        assert self.L.sfn_scal(self.h, a, out.ctypes.data) == 0
+        assert self.L.sfe_scal(self.h, a, out.ctypes.data) == 0
         return out
 
 
@@ -119,12 +82,12 @@ SC_ZWN, SC_PWN = 18, 19  # sf_types.hpp
 
 
 @pytest.mark.parametrize("name", ["lds-nb1", "hbm-bm", "hbm", "zl", "solo", "kits"])
-def test_emulated_copies_equal_the_restatement(shim, name):
+def test_emulated_copies_equal_the_restatement(name):
     A = 2 if name == "zl" else 3
     w = rc.workload(name, A)
     n = w.cfg.n_agents
     tb, sr = w.seeds()
-    e, ref = EmuSnap(w, shim), SnapshotRef(w, tb, sr, slots=4)
+    e, ref = EmuSnap(w), SnapshotRef(w, tb, sr, slots=4)
     snap = e.snapshot(4)
     assert snap.blob_bytes == snap.device_bytes - 4 + abi.SNAPSHOT_BLOB_HEADER
     e.reset(tb, sr)
@@ -166,12 +129,12 @@ def test_emulated_copies_equal_the_restatement(shim, name):
     took = sc.load_both(e, snap, ref, [-1] + [1] * (A - 1), "fork slot 1 into the others")
     assert took.tolist() == [False] + [True] * (A - 1)
     sc.steps_both(e, ref, cmds[at:at + 20], "the forks on commands of their own")
-    assert shim.sfn_last_parts(e.h) >= 1
+    assert e.L.sfe_last_parts(e.h) >= 1
     snap.close(), e.close(), ref.close()
 
 
 @pytest.mark.parametrize("rows,cols", [(9, 7), (10, 7), (12, 6)])
-def test_cell_counts_that_take_the_narrow_paths(shim, rows, cols):
+def test_cell_counts_that_take_the_narrow_paths(rows, cols):
     """63 cells: the damage plane goes by dwords, the exit-number plane by 16-bit words, and odd arenas' rows of it start
     off a dword; 70 cells: both by dwords; 72 cells: the exit-number plane 16 bytes at a time, the damage plane by dwords.
     One human (rows of 4 bytes) beside twelve (rows of 48)."""
@@ -182,7 +145,7 @@ def test_cell_counts_that_take_the_narrow_paths(shim, rows, cols):
     m, p = config.synthetic_map(rows, cols, wall_p=0.05, portal_pairs=1)
     w = config.Workload("narrow", cfg, m, p)
     tb, sr = w.seeds()
-    e, ref = EmuSnap(w, shim), SnapshotRef(w, tb, sr, slots=3)
+    e, ref = EmuSnap(w), SnapshotRef(w, tb, sr, slots=3)
     snap = e.snapshot(3)
     e.reset(tb, sr)
     cmds = rc.commands("solo", A, 1, 100)
@@ -195,11 +158,11 @@ def test_cell_counts_that_take_the_narrow_paths(shim, rows, cols):
     snap.close(), e.close(), ref.close()
 
 
-def test_bad_indices_and_blobs(shim):
+def test_bad_indices_and_blobs():
     A = 5
     w = rc.workload("solo", A)
     tb, sr = w.seeds()
-    e, ref = EmuSnap(w, shim), SnapshotRef(w, tb, sr, slots=3)
+    e, ref = EmuSnap(w), SnapshotRef(w, tb, sr, slots=3)
     snap = e.snapshot(3)
     e.reset(tb, sr)
     cmds = rc.commands("solo", A, 1, 40)
@@ -228,7 +191,7 @@ def test_bad_indices_and_blobs(shim):
     sc.steps_both(e, ref, cmds[20:30], "behind the import")
     w2 = rc.workload("solo", 2)
     w2.cfg.reseed_stride = A  # (the effective stride is part of the fingerprint: the default is the arena count)
-    e2 = EmuSnap(w2, shim)
+    e2 = EmuSnap(w2)
     snap2 = e2.snapshot(1)
     e2.reset(*w2.seeds())
     snap2.import_(0, blob)
@@ -236,32 +199,32 @@ def test_bad_indices_and_blobs(shim):
     assert (e2.digest() == at_save).all()
     w3 = rc.workload("solo", 2, auto_reset=1)
     w3.cfg.reseed_stride = A
-    e3 = EmuSnap(w3, shim)
+    e3 = EmuSnap(w3)
     snap3 = e3.snapshot(1)
-    assert snap3.import_rc(0, blob) == SF_ERR_ARG and b"configuration" in shim.sfn_last_error()
+    assert snap3.import_rc(0, blob) == SF_ERR_ARG and b"configuration" in e.L.sfe_last_error()
     for x in (snap, snap2, snap3, e, e2, e3, ref):
         x.close()
 
 
-def test_refusals(shim):
+def test_refusals():
     w = rc.workload("solo", 2)
-    e, other = EmuSnap(w, shim), EmuSnap(w, shim)
+    e, other = EmuSnap(w), EmuSnap(w)
     h = C.c_void_p()
-    assert shim.sfn_snapshot_create(e.h, 0, C.byref(h)) == SF_ERR_ARG and shim.sfn_snapshot_create(e.h, -1, C.byref(h)) == SF_ERR_ARG
-    assert shim.sfn_snapshot_create(e.h, 1, None) == SF_ERR_ARG
+    assert e.L.sfe_snapshot_create(e.h, 0, C.byref(h)) == SF_ERR_ARG and e.L.sfe_snapshot_create(e.h, -1, C.byref(h)) == SF_ERR_ARG
+    assert e.L.sfe_snapshot_create(e.h, 1, None) == SF_ERR_ARG
     snap, row = e.snapshot(2), sc.idx([0, 1])
     assert snap.save_rc(row) == SF_ERR_STATE and snap.load_rc(row) == SF_ERR_STATE  # before the first sf_reset
     e.reset(*w.seeds()), other.reset(*w.seeds())
     assert snap.save_rc(None) == SF_ERR_ARG and snap.load_rc(None) == SF_ERR_ARG
-    assert shim.sfn_snapshot_save(e.h, None, row.ctypes.data) == SF_ERR_ARG
-    assert shim.sfn_snapshot_save(other.h, snap.h, row.ctypes.data) == SF_ERR_STATE  # another environment's snapshot
-    assert shim.sfn_snapshot_load(other.h, snap.h, row.ctypes.data) == SF_ERR_STATE
+    assert e.L.sfe_snapshot_save(e.h, None, row.ctypes.data) == SF_ERR_ARG
+    assert e.L.sfe_snapshot_save(other.h, snap.h, row.ctypes.data) == SF_ERR_STATE  # another environment's snapshot
+    assert e.L.sfe_snapshot_load(other.h, snap.h, row.ctypes.data) == SF_ERR_STATE
     e.step_begin()
     assert snap.save_rc(row) == SF_ERR_STATE and snap.load_rc(row) == SF_ERR_STATE
     e.step_end(np.full((2, 1), ord("+"), dtype=np.uint8))
     stream, off = np.frombuffer(b"++", dtype=np.uint8), np.array([0, 1, 2], dtype=np.int64)
-    assert shim.sfn_replay_load(e.h, stream.ctypes.data, off.ctypes.data) == 0
+    assert e.L.sfe_replay_load(e.h, stream.ctypes.data, off.ctypes.data) == 0
     assert snap.save_rc(row) == SF_ERR_STATE and snap.load_rc(row) == SF_ERR_STATE  # while a replay is loaded
-    assert shim.sfn_replay_load(e.h, None, None) == 0
+    assert e.L.sfe_replay_load(e.h, None, None) == 0
     assert snap.save_rc(row) == 0 and snap.load_rc(row) == 0 and snap.status() == (0, 0)
     snap.close(), e.close(), other.close()

@@ -1,5 +1,5 @@
-"""The fixed instances' step loop on the wave emulator (tests/fixed_shape_emu: Core<WaveEmu, .., FixedShape<..>>, the body
-of k_step_fixed) at the places where it differs from the generic loop: restarts run by the loop itself, on a side
+"""The fixed instances' step loop on the wave emulator (tests/emu: Core<WaveEmu, .., FixedShape<..>>, the body of
+k_step_fixed) at the places where it differs from the generic loop: restarts run by the loop itself, on a side
 branch; a command pointer that runs to its end in place of the step number; frame % {30, 40, 50} kept as counters from
 load() on.  Every case of tests/step_fixed_lean_cases.py at 8 arenas, every launch plan: after each launch the fixed instance
 equals the oracle's digest of that step and the generic instance run through the same launches; with launches of one step
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import step_fixed_lean_cases as lean
-from test_fixed_shape_emu import EmuFixed, shim  # noqa: F401  (the shim fixture)
+from test_fixed_shape_emu import EmuFixed
 
 ARENAS = 8
 _runs = {}
@@ -36,14 +36,14 @@ def test_the_oracle_run_ends_the_games_the_case_is_about(name):
 
 
 @pytest.mark.parametrize("name,plan", [(n, p) for n in sorted(lean.CASES) for p in lean.CASES[n][4]])
-def test_fixed_step_loop_equals_oracle_and_generic_core(shim, name, plan, monkeypatch):  # noqa: F811
+def test_fixed_step_loop_equals_oracle_and_generic_core(name, plan, monkeypatch):
     world, commands, steps, kernel, plans, _ = lean.CASES[name]
     r = _oracle(name)
     monkeypatch.delenv("SF_STEP_GENERIC", raising=False)
     w = world(ARENAS)
-    f = EmuFixed(w, shim)
+    f = EmuFixed(w)
     monkeypatch.setenv("SF_STEP_GENERIC", "1")
-    g = EmuFixed(world(ARENAS), shim)
+    g = EmuFixed(world(ARENAS))
     monkeypatch.delenv("SF_STEP_GENERIC")
     tb, sr = w.seeds()
     f.reset(tb, sr), g.reset(tb, sr)
