@@ -536,6 +536,55 @@ int sf_dump_arena(sf_env *env, int32_t arena, sf_arena_hdr *hdr, sf_human_rec *h
                   sf_zombie_rec *zombies, sf_bullet_rec *bullets, sf_portal_rec *portals,
                   uint8_t *cell_flags, int32_t *cell_dmg, int32_t *cell_portal);
 
+/* ---- whole-arena state records and digests, on the device ------------------------------------------------------------
+ * sf_dump_arena shows one arena per call through a host copy of every arena's state.  sf_state_device decodes the same
+ * records where the state lives: for every arena (or the arenas an id list names) at once, in stream order, into device
+ * buffers the caller owns.  Every output is optional; a NULL one costs nothing.
+ *   Records.  Row i's sf_arena_hdr [gameplay.hpp:461, random.hpp:29-31], sf_human_rec [Character.hpp:65,286-294, the
+ *     mh / remote bitsets gameplay.hpp:55], sf_zombie_rec, sf_bullet_rec [gameplay.hpp:814-816,1087-1089], sf_portal_rec
+ *     and the three per-cell tables equal, word for word, what sf_dump_arena writes for that arena at that point of the
+ *     stream: the all-zero record of a slot that is not alive (zombies, bullets) or not active (exits), the all-zero
+ *     position / vec / ind / portal_ind of a human slot never used, the generator words masked to 20 bits, cell_dmg 0 off
+ *     a player-built (SF_CELL_TEMP) cell, and cell_portal -1 off an entrance, the side table's exit number on a
+ *     player-built entrance and the map's on a map entrance.
+ *   Cuts.  humans / zombies / bullets / portals say how many slots per row the four tables hold, 0 .. the
+ *     configuration's cap; a table cut below the cap shows the first that many slots, and nothing behind a row's last
+ *     requested slot is written.
+ *   d_counts, SF_STATE_COUNT_WORDS x int32 per row: alive humans, alive zombies, alive bullets, active exits | per table
+ *     the highest alive / active slot + 1, 0 if none.  Counted over the configuration's whole pools whatever the cuts: a
+ *     caller that sees extent > zombies knows the cut lost something, and sizes its tables by the extents, not the cap.
+ *   d_digest: sf_state_digest's value of that arena, bit for bit, always over the whole pools.
+ *   d_arena_ids: row i shows arena d_arena_ids[i]; duplicates are fine.  An id outside [0, arenas) never becomes an
+ *     address: every requested output of its row is zero, its eight counts are -1 and its digest is 0.
+ * The call writes nothing of the environment: digests, dumps and the next step are as without it.  It is allowed wherever
+ * sf_dump_arena is, also between sf_step_begin and sf_step_end.  It is one kernel launch on the environment's stream, two
+ * when d_counts or d_digest is asked for (their rows are zeroed first), in stream order: no allocation, no copy, no host
+ * synchronisation; the struct travels in the kernel arguments (it may be a temporary) and the call may be captured in a
+ * graph behind sf_step_device.  All outputs NULL: SF_OK, nothing launched.
+ * sf_state_bytes: the bytes each of the ten outputs must hold for this struct (d_hdr, d_humans, d_zombies, d_bullets,
+ * d_portals, d_cell_flags, d_cell_dmg, d_cell_portal, d_counts, d_digest, whether or not the pointer is set); no launch.
+ * SF_ERR_STATE: before the first sf_reset.  SF_ERR_ARG: null handles, rows < 1 with ids, a cut below 0 or above its cap,
+ * or a non-NULL pointer that is not device memory of the environment's device, is not aligned (8 bytes d_hdr and
+ * d_digest, 1 d_cell_flags, 4 the others) or whose extent reaches past its allocation; nothing is launched then. */
+#define SF_STATE_COUNT_WORDS 8
+typedef struct sf_state_io {
+  const int32_t *d_arena_ids;   /* optional, device, [rows]: row i shows arena d_arena_ids[i]; NULL: rows == arenas, row i = arena i */
+  int32_t rows;                 /* ignored when d_arena_ids == NULL */
+  int32_t humans, zombies, bullets, portals;  /* slots per row in the four tables below: 0 .. the configuration's cap */
+  sf_arena_hdr  *d_hdr;         /* optional, [rows] */
+  sf_human_rec  *d_humans;      /* optional, [rows][humans]  */
+  sf_zombie_rec *d_zombies;     /* optional, [rows][zombies] */
+  sf_bullet_rec *d_bullets;     /* optional, [rows][bullets] */
+  sf_portal_rec *d_portals;     /* optional, [rows][portals] */
+  uint8_t *d_cell_flags;        /* optional, [rows][floors*rows*cols] */
+  int32_t *d_cell_dmg;          /* optional, same shape */
+  int32_t *d_cell_portal;       /* optional, same shape */
+  int32_t *d_counts;            /* optional, [rows][SF_STATE_COUNT_WORDS] */
+  uint64_t *d_digest;           /* optional, [rows] */
+} sf_state_io;
+int sf_state_device(sf_env *env, const sf_state_io *io);
+int sf_state_bytes(sf_env *env, const sf_state_io *io, int64_t bytes_out[10]);
+
 /* Stream control: the library launches on this hipStream_t (passed as void*); NULL = default stream. */
 int sf_set_stream(sf_env *env, void *hip_stream);
 int sf_synchronize(sf_env *env);

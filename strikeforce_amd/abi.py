@@ -196,6 +196,36 @@ def bind_signals(lib, prefix):
     return lib
 
 
+STATE_COUNT_WORDS = 8  # SF_STATE_COUNT_WORDS
+STATE_COUNT_FIELDS = ("humans_alive", "zombies_alive", "bullets_alive", "portals_active",
+                      "humans_extent", "zombies_extent", "bullets_extent", "portals_extent")
+STATE_OUTPUTS = ("d_hdr", "d_humans", "d_zombies", "d_bullets", "d_portals", "d_cell_flags", "d_cell_dmg", "d_cell_portal",
+                 "d_counts", "d_digest")  # the order of sf_state_bytes' ten sizes
+STATE_EXPORTS = ("state_device", "state_bytes")
+
+
+class StateIO(C.Structure):
+    """sf_state_io: the id list, the cuts and the optional outputs of one sf_state_device (device pointers as integers)."""
+    _fields_ = [("d_arena_ids", C.c_void_p), ("rows", C.c_int32),
+                ("humans", C.c_int32), ("zombies", C.c_int32), ("bullets", C.c_int32), ("portals", C.c_int32)] + [
+        (n, C.c_void_p) for n in STATE_OUTPUTS]
+
+
+def bind_state(lib, prefix):
+    """Declare sf_state_device / sf_state_bytes (strikeforce.h) on a loaded library; handles and pointers as integers."""
+    g = lambda n: getattr(lib, prefix + n)
+    g("state_device").argtypes = [C.c_void_p, C.POINTER(StateIO)]
+    g("state_bytes").argtypes = [C.c_void_p, C.POINTER(StateIO), C.POINTER(C.c_int64 * 10)]
+    for n in STATE_EXPORTS:
+        g(n).restype = C.c_int
+    return lib
+
+
+def record_fields(struct):
+    """(name, first int32 word, words) of every field of a record structure, in layout order."""
+    return [(n, getattr(struct, n).offset // 4, getattr(struct, n).size // 4) for n, _ in struct._fields_]
+
+
 def struct_to_dict(s):
     out = {}
     for name, _ in s._fields_:

@@ -6,6 +6,7 @@
 //   k_rank (k_step's launch order) and the episode-log collection kernels k_ep_plan / k_ep_copy
 //   k_snapshot<SAVE>, the copy between the state buffers and a snapshot object (sf_snapshot.hpp)
 //   k_signals, vitals / delta / reward per (arena, agent) behind a step (sf_signals.hpp)
+//   k_state_init / k_state_records, every arena's canonical records, counts and digest (sf_state_records.hpp)
 //   HipRT, the runtime Env<RT> (sf_host.hpp) launches through
 //   Comm, the RCCL exchange of the multi-GPU path
 //   the extern "C" entry points
@@ -266,6 +267,16 @@ __global__ __launch_bounds__(256) void k_signals(Signals s) {
   signals_agent(s, i);
 }
 
+// sf_state_device (sf_state_records.hpp): grid (rows, parts), one wavefront per workgroup as in k_snapshot; k_state_init
+// zeroes the count and digest rows the wavefronts of one row add into, in front of it on the same stream.
+__global__ __launch_bounds__(256) void k_state_init(sf_state_io io) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < io.rows) state_init_body(io, i);
+}
+__global__ __launch_bounds__(64) void k_state_records(StateRec s) {
+  state_records_body(s, (int)blockIdx.x, (int)blockIdx.y);
+}
+
 #define SF_HIP(call)                                                                       \
   do {                                                                                     \
     hipError_t e_ = (call);                                                                \
@@ -376,6 +387,29 @@ struct HipRT {
     if (k.reward && (rc = check_device_range(k.reward, n * sizeof(float), 4, "d_reward", "sf_signals_step"))) return rc;
     if (k.rebase && (rc = check_device_range(k.rebase, n, 1, "d_rebase", "sf_signals_step"))) return rc;
     return launch(k_signals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k);
+  }
+  // sf_state_device: the id list and every requested output checked as sf_signals_step checks its own, then k_state_init
+  // (only with d_counts or d_digest) and k_state_records.  bytes: what each of the ten outputs must hold (Env::state_fill)
+  int launch_state_records(const StateRec &k, const int64_t *bytes) {
+    SF_HIP(hipSetDevice(device));
+    const sf_state_io &io = k.io;
+    const char *who = "sf_state_device";
+    int rc;
+    if (io.d_arena_ids && (rc = check_device_range(io.d_arena_ids, (size_t)io.rows * sizeof(int32_t), 4, "d_arena_ids", who))) return rc;
+    const struct { const void *q; size_t align; const char *name; } outs[10] = {
+        {io.d_hdr, 8, "d_hdr"}, {io.d_humans, 4, "d_humans"}, {io.d_zombies, 4, "d_zombies"}, {io.d_bullets, 4, "d_bullets"},
+        {io.d_portals, 4, "d_portals"}, {io.d_cell_flags, 1, "d_cell_flags"}, {io.d_cell_dmg, 4, "d_cell_dmg"},
+        {io.d_cell_portal, 4, "d_cell_portal"}, {io.d_counts, 4, "d_counts"}, {io.d_digest, 8, "d_digest"}};
+    bool any = false;
+    for (int j = 0; j < 10; ++j) {
+      if (!outs[j].q) continue;
+      any = true;
+      if ((rc = check_device_range(outs[j].q, (size_t)bytes[j], outs[j].align, outs[j].name, who))) return rc;
+    }
+    if (!any) return SF_OK;
+    if (io.d_counts || io.d_digest)
+      if ((rc = launch(k_state_init, dim3((unsigned)((io.rows + 255) / 256)), dim3(256), 0, io))) return rc;
+    return launch(k_state_records, dim3((unsigned)io.rows, (unsigned)k.parts), dim3(64), 0, k);
   }
   bool can_rank() const { return true; }
   // k_rank runs right in front of the k_step launch it orders, inside that launch's pair of timing events: what
@@ -851,6 +885,14 @@ int sf_dump_arena(sf_env *env, int32_t arena, sf_arena_hdr *hdr, sf_human_rec *h
                   int32_t *cell_portal) {
   SF_ENV(env);
   return env->e.dump_arena(arena, hdr, humans, zombies, bullets, portals, cell_flags, cell_dmg, cell_portal);
+}
+int sf_state_device(sf_env *env, const sf_state_io *io) {
+  SF_ENV(env);
+  return env->e.state_device(io);
+}
+int sf_state_bytes(sf_env *env, const sf_state_io *io, int64_t bytes_out[10]) {
+  SF_ENV(env);
+  return env->e.state_bytes(io, bytes_out);
 }
 int sf_set_stream(sf_env *env, void *hip_stream) {
   SF_ENV(env);

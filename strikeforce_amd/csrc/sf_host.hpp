@@ -21,6 +21,7 @@
 #include "sf_obs.hpp"
 #include "sf_snapshot_blob.hpp"
 #include "sf_signals.hpp"
+#include "sf_state_records.hpp"
 
 namespace sf {
 
@@ -182,18 +183,15 @@ inline int validate(const sf_config *c) {
   return SF_OK;
 }
 
-// splitmix64 finalizer; the digest is an order-independent sum of per-item hashes
-inline uint64_t mix64(uint64_t x) {
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ULL;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebULL;
-  x ^= x >> 31;
-  return x;
-}
-inline uint64_t dg(uint64_t tag, uint64_t idx, int64_t v) {
-  return mix64((tag << 56) ^ (idx << 32) ^ (uint64_t)(uint32_t)v ^ ((uint64_t)(v >> 32) << 40));
-}
+// (mix64 / dg, the digest's hash, and the record decoders are in sf_state_records.hpp: the device compiles them too)
+
+// whether a runtime has the state-record kernels (sf_state_device: k_state_init, k_state_records).  The HIP runtime has
+// them; the wave emulator's runtime of tests/emu does not, and sf_state_device answers SF_ERR_STATE there
+template <class R, class = void>
+struct has_state_records : std::false_type {};
+template <class R>
+struct has_state_records<R, decltype((void)std::declval<R &>().launch_state_records(std::declval<const StateRec &>(), nullptr))>
+    : std::true_type {};
 
 // whether a runtime has the episode log's own kernels: k_step's LOG instance (chosen through ep_log_on) and k_ep_late (the
 // record behind k_reset and the split step's second half).  The HIP runtime has them; the wave emulator's runtime of
@@ -1005,108 +1003,53 @@ struct Env {
     return rt.sync();
   }
 
-  // decode arena `a` of the snapshot into the canonical records of strikeforce.h
+  // decode arena `a` of the snapshot into the canonical records of strikeforce.h: the per-record text is
+  // sf_state_records.hpp's, which k_state_records compiles too
   void decode(int a, sf_arena_hdr *hdr, sf_human_rec *hs, sf_zombie_rec *zs, sf_bullet_rec *bs, sf_portal_rec *ps,
               uint8_t *cf, int32_t *cd, int32_t *cp) const {
     const size_t A = (size_t)p.A;
     if (hdr) {
-      memset(hdr, 0, sizeof *hdr);
-      const int32_t *sc = &s_scal[(size_t)a * SC_WORDS];
-      hdr->frame = sc[SC_FRAME], hdr->kills = sc[SC_KILLS], hdr->teams_kills = sc[SC_TKILLS], hdr->loot = sc[SC_LOOT];
-      hdr->chests = sc[SC_CHESTS], hdr->jomle = (uint32_t)sc[SC_JOMLE], hdr->steps = sc[SC_STEPS];
-      hdr->episodes = sc[SC_EPISODES];
-      hdr->tb = (int64_t)(((uint64_t)(uint32_t)sc[SC_TB_HI] << 32) | (uint32_t)sc[SC_TB_LO]);
-      hdr->serial = (int64_t)(((uint64_t)(uint32_t)sc[SC_SR_HI] << 32) | (uint32_t)sc[SC_SR_LO]);
-      for (int i = 0; i < 18; ++i) hdr->rng[i] = (int32_t)(s_rng[(size_t)a * RNG_WORDS + i] & 0xfffffu);
-      hdr->done = sc[SC_DONE], hdr->outcome = sc[SC_OUTCOME];
+      int32_t hw[REC_HDR_WORDS];
+      for (int j = 0; j < REC_HDR_WORDS; ++j) hw[j] = hdr_word(j, &s_scal[(size_t)a * SC_WORDS], &s_rng[(size_t)a * RNG_WORDS]);
+      memcpy(hdr, hw, sizeof *hdr);
     }
     if (hs)
       for (int i = 0; i < p.H; ++i) {
-        auto w = [&](int f) { return s_hum[((size_t)f * A + a) * p.H + i]; };
-        sf_human_rec &o = hs[i];
-        memset(&o, 0, sizeof o);
-        const uint32_t fl = w(HW_FLAGS), q = w(HW_POS), bp = w(HW_BPK);
-        const bool placed = (fl & (HF_ALIVE | HF_OCC)) || w(HW_HP) || (fl & HF_WAY_MASK);
-        o.alive = !!(fl & HF_ALIVE), o.remote = !!(fl & HF_REMOTE), o.rnpc = !!(fl & HF_RNPC), o.profile = !!(fl & HF_PROF);
-        if (placed && q != POS_NONE) o.f = pos_f(q), o.r = pos_r(q), o.c = pos_c(q);
-        o.way = (int)(fl & HF_WAY_MASK), o.team = (int)((fl >> HF_TEAM_SH) & 255u);
-        o.hp = (int32_t)w(HW_HP), o.stamina = (int32_t)w(HW_STAMINA), o.mindamage = (int32_t)w(HW_MINDAMAGE);
-        o.kills = (int32_t)w(HW_KILLS), o.damage = (int32_t)w(HW_DAMAGE), o.effect = (int32_t)w(HW_EFFECT);
-        const bool made = (fl & HF_WAY_MASK) != 0;  // slots never used stay all-zero, like the oracle's memset
-        o.vec = made ? (int)((fl >> HF_VEC_SH) & 3u) - 1 : 0, o.ind = made ? (int)((fl >> HF_IND_SH) & 15u) - 1 : 0;
-        o.cons[0] = w(HW_CONS01) & 0xffff, o.cons[1] = w(HW_CONS01) >> 16, o.cons[2] = w(HW_CONS23) & 0xffff,
-        o.cons[3] = w(HW_CONS23) >> 16;
-        o.throw_cnt[0] = w(HW_THR01) & 0xffff, o.throw_cnt[1] = w(HW_THR01) >> 16, o.throw_cnt[2] = w(HW_THR23) & 0xffff,
-        o.throw_cnt[3] = w(HW_THR23) >> 16;
-        o.blocks = bp & 255u, o.portals = (bp >> 8) & 255u, o.portal_ind = made ? (int)((bp >> 16) & 255u) - 1 : 0;
+        uint32_t w[HW_WORDS];
+        for (int f = 0; f < HW_WORDS; ++f) w[f] = s_hum[((size_t)f * A + a) * p.H + i];
+        decode_human(w, hs[i]);
       }
     if (zs)
       for (int i = 0; i < p.Z; ++i) {
         auto w = [&](int f) { return s_zom[((size_t)f * A + a) * p.Z + i]; };
-        memset(&zs[i], 0, sizeof zs[i]);
-        const uint32_t zp = w(ZW_POS);
-        if (!(zp & ZF_ALIVE)) continue;
-        zs[i].alive = 1, zs[i].f = pos_f(zp), zs[i].r = pos_r(zp), zs[i].c = pos_c(zp);
-        zs[i].hp = (int32_t)w(ZW_HP), zs[i].mindamage = (int32_t)w(ZW_MINDAMAGE), zs[i].super_ = !!(zp & ZF_SUPER);
+        decode_zombie(w(ZW_POS), w(ZW_HP), w(ZW_MINDAMAGE), zs[i]);
       }
     if (bs)
       for (int i = 0; i < p.B; ++i) {
         auto w = [&](int f) { return s_bul[((size_t)f * A + a) * p.B + i]; };
-        memset(&bs[i], 0, sizeof bs[i]);
-        const uint32_t ba = w(BW_A);
-        if (!(ba & BA_ALIVE)) continue;
-        bs[i].alive = 1, bs[i].f = pos_f(ba), bs[i].r = pos_r(ba), bs[i].c = pos_c(ba);
-        bs[i].way = (int)((ba >> BA_WAY_SH) & 3u) + 1, bs[i].traveled = (int)(w(BW_C) >> 16);
-        bs[i].damage = (int32_t)w(BW_DAMAGE), bs[i].effect = (int32_t)(int16_t)(w(BW_B) & 0xffffu);
-        bs[i].range = (int)(w(BW_C) & 0xffffu), bs[i].owner = (int)(w(BW_B) >> 16), bs[i].ref = !!(ba & BA_REF);
+        decode_bullet(w(BW_A), w(BW_DAMAGE), w(BW_B), w(BW_C), bs[i]);
       }
     if (ps)
-      for (int i = 0; i < p.P; ++i) {
-        memset(&ps[i], 0, sizeof ps[i]);
-        const uint32_t pp = s_por[(size_t)a * p.P + i];
-        if (!(pp & PF_ACTIVE)) continue;
-        ps[i].active = 1, ps[i].f = pos_f(pp), ps[i].r = pos_r(pp), ps[i].c = pos_c(pp);
-      }
+      for (int i = 0; i < p.P; ++i) decode_portal(s_por[(size_t)a * p.P + i], ps[i]);
     for (int ci = 0; ci < cells; ++ci) {
       const uint8_t fl = s_flags[(size_t)a * p.cells_pad + ci];
       if (cf) cf[ci] = fl;
-      if (cd) cd[ci] = (fl & SF_CELL_TEMP) ? s_dmg[(size_t)a * cells + ci] : 0;
-      if (cp) {
-        int v = -1;
-        if (fl & (SF_CELL_PIN_UP | SF_CELL_PIN_DN)) v = (fl & SF_CELL_TEMP) ? s_pidx[(size_t)a * cells + ci] : map_pidx[ci];
-        cp[ci] = v;
-      }
+      if (cd) cd[ci] = cell_dmg_of(fl, s_dmg[(size_t)a * cells + ci]);
+      if (cp) cp[ci] = cell_portal_of(fl, s_pidx[(size_t)a * cells + ci], map_pidx[ci]);
     }
   }
 
   uint64_t digest_of(const sf_arena_hdr &hdr, const sf_human_rec *hs, const sf_zombie_rec *zs, const sf_bullet_rec *bs,
                      const sf_portal_rec *ps, const uint8_t *cf, const int32_t *cd, const int32_t *cp) const {
     uint64_t d = 0;
-    const int64_t hv[9] = {hdr.frame, hdr.kills, hdr.teams_kills, hdr.loot, hdr.chests, hdr.jomle, hdr.steps, hdr.done,
-                           hdr.outcome};
-    for (int i = 0; i < 9; ++i) d += dg(1, (uint64_t)i, hv[i]);
-    for (int i = 0; i < 18; ++i) d += dg(2, (uint64_t)i, hdr.rng[i]);
-    for (int i = 0; i < p.H; ++i) {
-      const int32_t *w = (const int32_t *)&hs[i];
-      for (size_t k = 0; k < sizeof(sf_human_rec) / 4; ++k) d += dg(3, (uint64_t)(i * 32 + (int)k), w[k]);
-    }
-    for (int i = 0; i < p.Z; ++i) {
-      const int32_t *w = (const int32_t *)&zs[i];
-      for (size_t k = 0; k < sizeof(sf_zombie_rec) / 4; ++k) d += dg(4, (uint64_t)(i * 8 + (int)k), w[k]);
-    }
-    for (int i = 0; i < p.B; ++i) {
-      const int32_t *w = (const int32_t *)&bs[i];
-      for (size_t k = 0; k < sizeof(sf_bullet_rec) / 4; ++k) d += dg(5, (uint64_t)(i * 16 + (int)k), w[k]);
-    }
-    for (int i = 0; i < p.P; ++i) {
-      const int32_t *w = (const int32_t *)&ps[i];
-      for (size_t k = 0; k < sizeof(sf_portal_rec) / 4; ++k) d += dg(6, (uint64_t)(i * 4 + (int)k), w[k]);
-    }
-    for (int ci = 0; ci < cells; ++ci) {
-      if (cf[ci]) d += dg(7, (uint64_t)ci, cf[ci]);
-      if (cd[ci]) d += dg(8, (uint64_t)ci, cd[ci]);
-      if (cp[ci] != -1) d += dg(9, (uint64_t)ci, cp[ci]);
-    }
+    int32_t hw[REC_HDR_WORDS];
+    memcpy(hw, &hdr, sizeof hdr);
+    for (int j = 0; j < DG_HDR_TERMS; ++j) d += digest_hdr_term(j, hw);
+    for (int i = 0; i < p.H; ++i) d += digest_human(i, hs[i]);
+    for (int i = 0; i < p.Z; ++i) d += digest_zombie(i, zs[i]);
+    for (int i = 0; i < p.B; ++i) d += digest_bullet(i, bs[i]);
+    for (int i = 0; i < p.P; ++i) d += digest_portal(i, ps[i]);
+    for (int ci = 0; ci < cells; ++ci) d += digest_cell(ci, cf[ci], cd[ci], cp[ci]);
     return d;
   }
 
@@ -1137,6 +1080,46 @@ struct Env {
       out[a] = digest_of(hdr, hs.data(), zs.data(), bs.data(), ps.data(), cf.data(), cd.data(), cp.data());
     }
     return SF_OK;
+  }
+
+  // sf_state_device / sf_state_bytes: the kernel's struct and the bytes each of the ten outputs must hold
+  int state_fill(const sf_state_io *io, StateRec &k, int64_t bytes[10], const char *who) const {
+    if (!io) return fail(SF_ERR_ARG, std::string(who) + ": null argument");
+    if (!was_reset) return fail(SF_ERR_STATE, std::string(who) + " before sf_reset");
+    if (io->d_arena_ids && io->rows < 1) return fail(SF_ERR_ARG, std::string(who) + ": rows must be at least 1 with d_arena_ids");
+    if (io->humans < 0 || io->humans > p.H || io->zombies < 0 || io->zombies > p.Z || io->bullets < 0 || io->bullets > p.B ||
+        io->portals < 0 || io->portals > p.P)
+      return fail(SF_ERR_ARG, std::string(who) + ": humans / zombies / bullets / portals must be 0 .. the configuration's cap");
+    memset(&k, 0, sizeof k);
+    k.hum = p.hum, k.zom = p.zom, k.bul = p.bul, k.por = p.por, k.rng = p.rng, k.scal = p.scal, k.flags = p.flags;
+    k.aux_dmg = p.aux_dmg, k.aux_pidx = p.aux_pidx, k.map_pidx = p.map_pidx;
+    k.A = p.A, k.H = p.H, k.Z = p.Z, k.B = p.B, k.P = p.P, k.cells = cells, k.cells_pad = p.cells_pad;
+    k.io = *io;
+    if (!io->d_arena_ids) k.io.rows = p.A;
+    k.parts = state_parts_for(state_units(k).total(), k.io.rows);
+    const int64_t R = k.io.rows, C = cells;
+    const int64_t b[10] = {R * (int64_t)sizeof(sf_arena_hdr), R * io->humans * (int64_t)sizeof(sf_human_rec),
+                           R * io->zombies * (int64_t)sizeof(sf_zombie_rec), R * io->bullets * (int64_t)sizeof(sf_bullet_rec),
+                           R * io->portals * (int64_t)sizeof(sf_portal_rec), R * C, R * C * 4, R * C * 4,
+                           R * SF_STATE_COUNT_WORDS * 4, R * 8};
+    memcpy(bytes, b, sizeof b);
+    return SF_OK;
+  }
+  int state_bytes(const sf_state_io *io, int64_t *out) const {
+    if (!out) return fail(SF_ERR_ARG, "sf_state_bytes: null argument");
+    StateRec k;
+    return state_fill(io, k, out, "sf_state_bytes");
+  }
+  // one or two stream-ordered launches; nothing is allocated, copied or waited for
+  int state_device(const sf_state_io *io) {
+    StateRec k;
+    int64_t bytes[10];
+    if (int rc = state_fill(io, k, bytes, "sf_state_device")) return rc;
+    if constexpr (has_state_records<RT>::value) {
+      return rt.launch_state_records(k, bytes);
+    } else {
+      return fail(SF_ERR_STATE, "sf_state_device: this runtime has no state-record kernels");
+    }
   }
 };
 

@@ -76,6 +76,8 @@ def load_library():
             abi.bind_snapshot(L, "sf_")
         if hasattr(L, "sf_signals_create"):  # (per-step signals; an older build loaded through SF_LIBRARY_PATH lacks them)
             abi.bind_signals(L, "sf_")
+        if hasattr(L, "sf_state_device"):  # (state records on the device; an older build loaded through SF_LIBRARY_PATH lacks them)
+            abi.bind_state(L, "sf_")
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -113,7 +115,7 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
            "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device",
-           "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS + abi.SIGNALS_EXPORTS]
+           "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS + abi.SIGNALS_EXPORTS + abi.STATE_EXPORTS]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -248,6 +250,29 @@ def decode_signals(vitals=None, delta=None):
     return out
 
 
+def decode_state(hdr=None, humans=None, zombies=None, bullets=None, portals=None, counts=None):
+    """Named views of sf_state_device's record outputs, torch tensors or numpy arrays alike, nothing copied: each table
+    int32 [..., words of its record] -> {field: int32 [...]} (cons / throw_cnt keep a last axis of 4) under "humans",
+    "zombies", "bullets", "portals"; hdr int32 [rows][40] -> "hdr": the ten 64-bit fields as int64 [rows], rng int32
+    [rows][18], done, outcome; counts int32 [rows][8] -> "counts": abi.STATE_COUNT_FIELDS.  -> {table: {field: view}}"""
+    out = {}
+    for name, t, struct in (("humans", humans, abi.HumanRec), ("zombies", zombies, abi.ZombieRec),
+                            ("bullets", bullets, abi.BulletRec), ("portals", portals, abi.PortalRec)):
+        if t is not None:
+            assert t.shape[-1] == C.sizeof(struct) // 4
+            out[name] = {n: (t[..., w] if k == 1 else t[..., w:w + k]) for n, w, k in abi.record_fields(struct)}
+    if hdr is not None:
+        assert hdr.shape[-1] == C.sizeof(abi.ArenaHdr) // 4
+        i64 = hdr[..., :20].view(np.int64 if isinstance(hdr, np.ndarray) else __import__("torch").int64)
+        h = {n: i64[..., j] for j, (n, _) in enumerate(abi.ArenaHdr._fields_[:10])}
+        h.update(rng=hdr[..., 20:38], done=hdr[..., 38], outcome=hdr[..., 39])
+        out["hdr"] = h
+    if counts is not None:
+        assert counts.shape[-1] == abi.STATE_COUNT_WORDS
+        out["counts"] = {n: counts[..., j] for j, n in enumerate(abi.STATE_COUNT_FIELDS)}
+    return out
+
+
 class Signals:
     """Per-step game signals of every (arena, agent) on the device (strikeforce.h sf_signals_*): step() is one
     stream-ordered launch behind any step that writes, wherever a device address is given, the vitals (int32 [arenas]
@@ -358,6 +383,85 @@ class ArenaBatch:
     def signals(self):
         """Per-step vitals, deltas and a shaped reward on the device (sf_signals_create): see Signals."""
         return Signals(self)
+
+    def state_device(self, io):
+        """sf_state_device with a ready abi.StateIO: one or two stream-ordered launches, nothing else."""
+        if not hasattr(self.L, "sf_state_device"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_state_device")
+        self._ck(self.L.sf_state_device(self.h, C.byref(io)), "sf_state_device")
+
+    def state_bytes(self, io):
+        """The bytes each of the ten outputs of `io` must hold, in abi.STATE_OUTPUTS' order (sf_state_bytes)."""
+        out = (C.c_int64 * 10)()
+        self._ck(self.L.sf_state_bytes(self.h, C.byref(io), C.byref(out)), "sf_state_bytes")
+        return [int(x) for x in out]
+
+    def state_io(self, arena_ids=None, humans=None, zombies=None, bullets=None, portals=None, cells=False, hdr=True,
+                 counts=True, digest=False):
+        """The request of state_records() without the launch: (abi.StateIO, the dict state_records() returns).  Tensors,
+        struct and named views are built once per shape of request and kept; a later call of the same shape returns the
+        same objects (with its own arena_ids), so a loop pays for them once."""
+        import torch
+        cfg = self.cfg
+        dev = "cuda:%d" % cfg.device
+        ids = None
+        if arena_ids is not None:
+            ids = arena_ids if hasattr(arena_ids, "data_ptr") else torch.from_numpy(
+                np.ascontiguousarray(arena_ids, dtype=np.int32).reshape(-1)).to(dev)
+            if str(ids.dtype) != "torch.int32" or not ids.is_cuda or not ids.is_contiguous() or ids.dim() != 1:
+                raise ValueError("arena_ids must be a contiguous one-dimensional int32 tensor on the device")
+        rows = cfg.arenas if ids is None else int(ids.numel())
+        cut = tuple(cap if n is None else int(n) for n, cap in ((humans, cfg.cap_humans), (zombies, cfg.cap_zombies),
+                                                                (bullets, cfg.cap_bullets), (portals, cfg.cap_portals)))
+        key = (rows, ids is not None, cut, bool(cells), bool(hdr), bool(counts), bool(digest))
+        cache = self.__dict__.setdefault("_state_requests", {})
+        if key not in cache:
+            ncell = cfg.floors * cfg.rows * cfg.cols
+            new = lambda shape, dtype=torch.int32: torch.zeros(shape, dtype=dtype, device=dev)
+            raw = {}
+            if hdr:
+                raw["hdr"] = new((rows, 40))
+            for name, n, words in (("humans", cut[0], 28), ("zombies", cut[1], 7), ("bullets", cut[2], 11), ("portals", cut[3], 4)):
+                if n:
+                    raw[name] = new((rows, n, words))
+            if cells:
+                raw["cell_flags"] = new((rows, ncell), torch.uint8)
+                raw["cell_dmg"], raw["cell_portal"] = new((rows, ncell)), new((rows, ncell))
+            if counts:
+                raw["counts"] = new((rows, abi.STATE_COUNT_WORDS))
+            if digest:
+                raw["digest"] = new((rows,), torch.int64)
+            io = abi.StateIO()
+            io.humans, io.zombies, io.bullets, io.portals = cut
+            for n in abi.STATE_OUTPUTS:
+                if n[2:] in raw:
+                    setattr(io, n, raw[n[2:]].data_ptr())
+            out = decode_state(*[raw.get(n) for n in ("hdr", "humans", "zombies", "bullets", "portals", "counts")])
+            out["raw"] = raw
+            cache[key] = (io, out)
+        io, out = cache[key]
+        if ids is not None:
+            io.d_arena_ids, io.rows = ids.data_ptr(), rows
+            out["arena_ids"] = ids  # (alive as long as the request: the launch may still be queued)
+        return io, out
+
+    def state_records(self, arena_ids=None, humans=None, zombies=None, bullets=None, portals=None, cells=False, hdr=True,
+                      counts=True, digest=False):
+        """Every arena's canonical records on the device (sf_state_device), as torch tensors that are allocated once per
+        shape of request and rewritten by every later call of the same shape.  arena_ids: None (row i = arena i), a torch
+        int32 tensor on the device, or a host sequence (uploaded on every call).  humans / zombies / bullets / portals:
+        slots per row, None = the configuration's cap, 0 = leave the table out.  -> a dict: the raw tensors under "raw"
+        (hdr int32 [rows][40], humans [rows][n][28], zombies [rows][n][7], bullets [rows][n][11], portals [rows][n][4],
+        cell_flags uint8 / cell_dmg / cell_portal int32 [rows][cells], counts int32 [rows][8], digest int64 [rows]: the
+        bits of the unsigned value) and the named views of decode_state().  Nothing is read on the host."""
+        io, out = self.state_io(arena_ids, humans, zombies, bullets, portals, cells, hdr, counts, digest)
+        self.state_device(io)
+        return out
+
+    def digest_device(self):
+        """sf_state_digest's values computed on the device, in stream order: an int64 tensor [arenas] holding the bits of
+        the unsigned digests (`.cpu().numpy().view(numpy.uint64)` equals digest()).  The same tensor is rewritten by every call."""
+        return self.state_records(humans=0, zombies=0, bullets=0, portals=0, hdr=False, counts=False, digest=True)["raw"]["digest"]
 
     def snapshot_slot_bytes(self):
         """(device bytes, blob bytes) one snapshot slot of this configuration takes: to budget before snapshot()."""
