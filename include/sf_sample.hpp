@@ -26,7 +26,8 @@
 // the reference logged replays here: tests/test_cpp_sample.py does both against the reference's own build);
 // sf::replay feeds a sample to an sf_env through sf_reset / sf_step / sf_done, a match through the split step
 // (sf_step_begin / sf_agent_alive / sf_step_end); sf::replay_on_device through sf_replay_load / sf_replay_step, the lines
-// fetched on the device.  Python twin: strikeforce_amd/replay.py.
+// fetched on the device; sf::samples_of_recording turns what a recorder collected (sf_record_collect: games played here,
+// written out on the device as these command lines) into Samples.  Python twin: strikeforce_amd/replay.py.
 #ifndef SF_SAMPLE_HPP
 #define SF_SAMPLE_HPP
 
@@ -293,6 +294,38 @@ inline long replay_on_device(sf_env *env, const Sample &s, ReplayEnd *end = null
   }
   if (end) end->state = st[0], end->cursor = st[1], end->iterations = st[2];
   return st[2];
+}
+
+// What a recorder says about one game beside its sample: the words of its game record that are no part of the file
+struct RecordedGame {
+  int32_t arena = 0, episode = 0, iterations = 0, end = 0 /* SF_RECORD_* */, outcome = SF_RUNNING;
+};
+
+// The games a recorder collected (sf_record_collect: `n_games` records of SF_RECORD_GAME_WORDS int32 and the streams back
+// to back, `n_bytes` of them) as Samples, one per game in the order delivered: seed and command stream from the recording;
+// players, `ind`, the teams, names and character records — which the recorder does not know — from `like` (a sample of a
+// match these games resemble, or one filled in by hand).  write_sample then produces files the reference reads.  Returns
+// false if a game's stream lies outside the bytes given.  Python twin: replay.samples_from_recording.
+inline bool samples_of_recording(const int32_t *games, int64_t n_games, const uint8_t *bytes, int64_t n_bytes, const Sample &like,
+                                 std::vector<Sample> &out, std::vector<RecordedGame> *info = nullptr) {
+  out.clear();
+  if (info) info->clear();
+  for (int64_t i = 0; i < n_games; ++i) {
+    const int32_t *g = games + i * SF_RECORD_GAME_WORDS;
+    auto u64 = [&](int lo) { return ((uint64_t)(uint32_t)g[lo + 1] << 32) | (uint64_t)(uint32_t)g[lo]; };
+    const int64_t off = (int64_t)u64(10), lines = g[6];
+    if (off < 0 || lines < 0 || off > n_bytes || lines > n_bytes - off) return false;
+    Sample s = like;
+    s.tb = u64(2), s.serial = u64(4);
+    s.commands.assign(reinterpret_cast<const char *>(bytes) + off, (size_t)lines);
+    out.push_back(s);
+    if (info) {
+      RecordedGame r;
+      r.arena = g[0], r.episode = g[1], r.iterations = g[7], r.end = g[8], r.outcome = g[9];
+      info->push_back(r);
+    }
+  }
+  return true;
 }
 
 }  // namespace sf

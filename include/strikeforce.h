@@ -484,6 +484,68 @@ int sf_replay_status(sf_env *env, int32_t *out_host);
 int sf_replay_status_device(sf_env *env, int32_t *d_out);
 int sf_replay_commands_device(sf_env *env, uint8_t *d_out);
 
+/* ---- recording of games as command streams, on the device ------------------------------------------------------------
+ * The reference writes a `.sf_sample` while a game is played: with `enable_logging`, human_action appends the command of
+ * `ind` (`log_file << command[ind]`, gameplay.hpp:966-967) and then one line for every other human with mh[i] && remote[i],
+ * slots ascending (gameplay.hpp:982-983, 990-991), behind the header load_data wrote (gameplay.hpp:1784-1794, 1836-1845,
+ * 1867-1869, 1910-1914).  How many lines an iteration has depends on who is alive after its first half, so the stream is
+ * written where the state is: sf_record_step is sf_replay_step's inverse.  A recorder belongs to one environment and owns,
+ * per arena, a region of bytes_per_arena bytes for the streams and an index of games_per_arena game records.
+ *
+ * sf_record_step plays one iteration of every arena, bit for bit what sf_step_device(d_cmd, 1) does to the environment
+ * (auto_reset, the result latch and the episode log included): a loop-top record launch, the first half (as
+ * sf_step_begin), a record launch between the halves (not where n_agents == 1), the second half (as sf_step_end_device)
+ * and a closing record launch: three small launches more than the split step, all on the environment's stream, no host
+ * synchronisation.  d_cmd: device, [arenas][n_agents], as for sf_step_end_device.  Per arena — the game it is writing is
+ * its open game:
+ *   - loop top.  A done arena writes nothing.  An open game that the arena was restarted under (steps == 0 again:
+ *     sf_reset_arenas, sf_reset) is closed as SF_RECORD_CUT — as SF_RECORD_BROKEN if sf_arena_hdr.episodes says that a game
+ *     ended in between, behind the recorder's back.  An open game whose iteration count differs from sf_arena_hdr.steps
+ *     (the arena was stepped through another entry point, or loaded from a snapshot), and one found open in a done arena
+ *     (the closing launch below closes every game this call ends: another call ended this one), is SF_RECORD_BROKEN.  An arena
+ *     without an open game opens one iff steps == 0: the record takes the arena, sf_arena_hdr.episodes and the running
+ *     seed.  An arena with steps != 0 and no open game records nothing until its next steps == 0.  Where the index is full
+ *     the game is not opened and counted as lost.  Then the command of `ind` is appended; this needs n_agents free bytes
+ *     in the region (a whole iteration), otherwise the game is closed as SF_RECORD_OVERFLOW with nothing of this iteration
+ *     written: a stream only ever holds whole iterations and never replays as SF_REPLAY_TRUNCATED.
+ *   - between the halves.  Every commanded human g != ind that sf_agent_alive would report (sf_replay_step's own
+ *     predicate: a dead player's slot re-used by a spawned NPC is not) appends its byte of d_cmd, slots ascending.
+ *   - closing.  A game that check_end ended in this iteration (gameplay.hpp:1450) is closed as SF_RECORD_GAME_ENDED with
+ *     its outcome (sf_arena_hdr.outcome; under auto_reset the latched result's).  GAME_ENDED is reported exactly then.
+ *   - a command byte <= 0x20 or >= 0x7f cannot stand in a sample (`operator>>` reads one token per command) and is
+ *     written as '+' and counted.  Every such byte acts as '+' in the step itself (obey, gameplay.hpp:695-821, knows its
+ *     command chars and ignores every other byte), so the stream still replays to the same game.
+ * sf_record_flush closes every open game as SF_RECORD_CUT (one launch); the arena records again from its next steps == 0.
+ *
+ * sf_record_collect_device delivers every CLOSED game, arena ascending and game ascending within an arena: d_games gets
+ * SF_RECORD_GAME_WORDS int32 per game — arena, episode, tb lo, hi, serial lo, hi, lines, iterations, end (SF_RECORD_*),
+ * outcome (SF_*; SF_RUNNING unless GAME_ENDED), byte offset lo, hi into d_bytes — and d_bytes the streams back to back:
+ * offsets and lines are what sf_replay_load takes as `offsets` / `streams`.  Delivery stops at the first game that does not
+ * fit max_bytes / max_games; it and every later game stay pending, the order is never broken.  The space of delivered
+ * games is free again; an open game goes on uninterrupted.  d_counts, int64 [6]: games delivered, bytes delivered, games
+ * pending, bytes pending, games lost to a full index and bytes substituted since the last collect.  Two launches on the
+ * environment's stream, no host synchronisation.  sf_record_collect is the same into host memory and synchronises.
+ * create and destroy synchronise.  Destroy a recorder before its environment.  While no recorder exists nothing is
+ * allocated and no other entry point behaves differently.
+ * Not recorded: iterations inside sf_step_device (any k) or sf_step / sf_step_begin; the continuation of a forked or loaded
+ * game (BROKEN).  The character records of a sample's header are the configuration's, not the recorder's.
+ * SF_ERR_STATE: before the first sf_reset, between sf_step_begin and sf_step_end, while a replay is loaded.  SF_ERR_ARG: null
+ * handles, a recorder of another environment, a null d_cmd, bytes_per_arena < n_agents or >= 2^31, games_per_arena < 1,
+ * max_bytes / max_games < 1, an output that is not device memory of the environment's device, is not aligned (d_games 4,
+ * d_counts 8) or shorter than max_bytes / max_games say; nothing is launched then. */
+#define SF_RECORD_GAME_WORDS 12
+#define SF_RECORD_COUNT_WORDS 6
+enum { SF_RECORD_GAME_ENDED = 1, SF_RECORD_CUT = 2, SF_RECORD_OVERFLOW = 3, SF_RECORD_BROKEN = 4 };
+typedef struct sf_recorder sf_recorder;        /* opaque; belongs to one env */
+int sf_record_create(sf_env *env, int64_t bytes_per_arena, int32_t games_per_arena, sf_recorder **out);
+int sf_record_destroy(sf_recorder *r);         /* before its env */
+int sf_record_step(sf_env *env, sf_recorder *r, const uint8_t *d_cmd);
+int sf_record_flush(sf_env *env, sf_recorder *r);
+int sf_record_collect_device(sf_recorder *r, uint8_t *d_bytes, int64_t max_bytes, int32_t *d_games, int32_t max_games,
+                             int64_t *d_counts);
+int sf_record_collect(sf_recorder *r, uint8_t *bytes_host, int64_t max_bytes, int32_t *games_host, int32_t max_games,
+                      int64_t *counts_host);
+
 /* ---- multi-GPU: the one exchange step ------------------------------------------
  * Arenas are sharded over one sf_env per GPU with no data-path collective.  The result records of all shards are
  * exchanged with an RCCL all-gather over xGMI.  The reference has no counterpart (its only inter-process traffic is the

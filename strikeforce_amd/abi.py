@@ -221,6 +221,27 @@ def bind_state(lib, prefix):
     return lib
 
 
+RECORD_GAME_WORDS, RECORD_COUNT_WORDS = 12, 6  # SF_RECORD_GAME_WORDS, SF_RECORD_COUNT_WORDS
+RECORD_GAME_ENDED, RECORD_CUT, RECORD_OVERFLOW, RECORD_BROKEN = 1, 2, 3, 4  # SF_RECORD_*
+RECORD_COUNT_FIELDS = ("games", "bytes", "games_pending", "bytes_pending", "games_lost", "bytes_substituted")
+RECORD_EXPORTS = ("record_create", "record_destroy", "record_step", "record_flush", "record_collect_device", "record_collect")
+
+
+def bind_record(lib, prefix):
+    """Declare the sf_record_* entry points (strikeforce.h) on a loaded library; handles and pointers as integers."""
+    g = lambda n: getattr(lib, prefix + n)
+    vp = C.c_void_p
+    g("record_create").argtypes = [vp, C.c_int64, C.c_int32, C.POINTER(vp)]
+    g("record_destroy").argtypes = [vp]
+    g("record_step").argtypes = [vp, vp, vp]
+    g("record_flush").argtypes = [vp, vp]
+    g("record_collect_device").argtypes = [vp, vp, C.c_int64, vp, C.c_int32, vp]
+    g("record_collect").argtypes = [vp, vp, C.c_int64, vp, C.c_int32, vp]
+    for n in RECORD_EXPORTS:
+        g(n).restype = C.c_int
+    return lib
+
+
 def record_fields(struct):
     """(name, first int32 word, words) of every field of a record structure, in layout order."""
     return [(n, getattr(struct, n).offset // 4, getattr(struct, n).size // 4) for n, _ in struct._fields_]

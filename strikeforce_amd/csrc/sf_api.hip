@@ -7,6 +7,7 @@
 //   k_snapshot<SAVE>, the copy between the state buffers and a snapshot object (sf_snapshot.hpp)
 //   k_signals, vitals / delta / reward per (arena, agent) behind a step (sf_signals.hpp)
 //   k_state_init / k_state_records, every arena's canonical records, counts and digest (sf_state_records.hpp)
+//   k_record, k_record_plan / k_record_copy, games written out as command streams and their collection (sf_record.hpp)
 //   HipRT, the runtime Env<RT> (sf_host.hpp) launches through
 //   Comm, the RCCL exchange of the multi-GPU path
 //   the extern "C" entry points
@@ -29,6 +30,7 @@
 #include "sf_obs_kernels.hpp"
 #include "sf_snapshot.hpp"
 #include "sf_signals.hpp"
+#include "sf_record.hpp"
 #include "sf_host.hpp"
 // clang-format on
 
@@ -277,6 +279,94 @@ __global__ __launch_bounds__(64) void k_state_records(StateRec s) {
   state_records_body(s, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+// sf_record_step / sf_record_flush (sf_record.hpp): one wavefront per arena and workgroup, lane g = commanded human g.
+// mode 0 the loop top, mode 1 between the halves, mode 2 behind the second half, mode 3 the flush.  Modes 0, 2 and 3 are
+// lane 0's alone.  Mode 1: one flag-word load, the ballot, the lane's rank in it, one byte store; the cursor by lane 0.
+__global__ __launch_bounds__(64) void k_record(Record k, int mode) {
+  const int a = (int)blockIdx.x, g = (int)threadIdx.x;
+  if (mode == 1) {
+    const bool takes = record_mid_takes(k, a, g);
+    const uint64_t bal = __ballot(takes);
+    if (!bal) return;
+    const bool sub = takes && record_mid_store(k, a, g, bal);
+    const uint64_t subs = __ballot(sub);
+    if (g == 0) record_mid_finish(k, a, __popcll(bal), __popcll(subs));
+    return;
+  }
+  if (g != 0) return;
+  if (mode == 0) record_top(k, a);
+  else if (mode == 2) record_end(k, a);
+  else record_flush(k, a);
+}
+
+// sf_record_collect_device, two launches as the episode log's collection (k_ep_plan / k_ep_copy).
+// k_record_plan: one 1024-thread workgroup, thread t owns a contiguous run of arenas.  The exclusive prefix sums of closed
+// games and closed bytes over arenas (per-thread sums, a scan of the 1024 sums in LDS) say for every game what lies in
+// front of it in the output order; record_plan_arena decides from that alone what its arena delivers.
+__global__ __launch_bounds__(1024) void k_record_plan(Record k, long long max_games, long long max_bytes, long long *counts) {
+  __shared__ long long sg[1024], sb[1024];
+  __shared__ unsigned long long tot[4];
+  const int t = (int)threadIdx.x;
+  const int chunk = (k.A + 1023) / 1024;
+  const int a0 = min(t * chunk, k.A), a1 = min(a0 + chunk, k.A);
+  int64_t g = 0, b = 0;
+  for (int a = a0; a < a1; ++a) {
+    int64_t ga, ba;
+    record_arena_totals(k, a, ga, ba);
+    g += ga, b += ba;
+  }
+  sg[t] = g, sb[t] = b;
+  if (t < 4) tot[t] = 0ull;
+  __syncthreads();
+  for (int d = 1; d < 1024; d <<= 1) {
+    const long long ug = t >= d ? sg[t - d] : 0, ub = t >= d ? sb[t - d] : 0;
+    __syncthreads();
+    sg[t] += ug, sb[t] += ub;
+    __syncthreads();
+  }
+  int64_t gpre = sg[t] - g, bpre = sb[t] - b;
+  const long long all_g = sg[1023], all_b = sb[1023];
+  int64_t tg = 0, tb = 0, lost = 0, subst = 0;
+  for (int a = a0; a < a1; ++a) {
+    int64_t ga, ba;
+    record_arena_totals(k, a, ga, ba);
+    record_plan_arena(k, a, gpre, bpre, max_games, max_bytes, tg, tb, lost, subst);
+    gpre += ga, bpre += ba;
+  }
+  if (tg) atomicAdd(&tot[0], (unsigned long long)tg);
+  if (tb) atomicAdd(&tot[1], (unsigned long long)tb);
+  if (lost) atomicAdd(&tot[2], (unsigned long long)lost);
+  if (subst) atomicAdd(&tot[3], (unsigned long long)subst);
+  __syncthreads();
+  if (t == 0) {
+    SF_GLOBAL long long *c = gptr(counts);
+    c[0] = (long long)tot[0], c[1] = (long long)tot[1], c[2] = all_g - (long long)tot[0], c[3] = all_b - (long long)tot[1];
+    c[4] = (long long)tot[2], c[5] = (long long)tot[3];
+  }
+}
+
+// k_record_copy: one wavefront per arena (four per workgroup).  Each pass stores 64 consecutive dwords of the dense game
+// list, then 64 consecutive bytes of the dense streams; then what stays moves to the front of the region and the index.
+__global__ __launch_bounds__(256) void k_record_copy(Record k, uint8_t *d_bytes, int32_t *d_games) {
+  const int a = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6), lane = (int)threadIdx.x & 63;
+  if (a >= k.A) return;
+  const RecordCopy c = record_copy_load(k, a);
+  if (c.ntake == 0) return;
+  for (int32_t i = lane; i < c.ntake * RG_WORDS; i += 64) record_copy_game_word(k, c, a, i, d_games);
+  for (int32_t i = lane; i < c.tbytes; i += 64) record_copy_byte(k, c, a, i, d_bytes);
+  const int32_t rem_w = (c.ngames - c.ntake) * RG_WORDS, rem_b = c.used - c.tbytes;
+  for (int32_t i = lane; i < rem_w; i += 64) {
+    const int32_t v = record_compact_word_load(k, c, a, i);
+    record_compact_word_store(k, a, i, v);
+  }
+  if (c.tbytes)
+    for (int32_t i = lane; i < rem_b; i += 64) {
+      const uint8_t v = record_compact_byte_load(k, c, a, i);
+      record_compact_byte_store(k, a, i, v);
+    }
+  if (lane == 0) record_copy_finish(k, c, a);
+}
+
 #define SF_HIP(call)                                                                       \
   do {                                                                                     \
     hipError_t e_ = (call);                                                                \
@@ -410,6 +500,24 @@ struct HipRT {
     if (io.d_counts || io.d_digest)
       if ((rc = launch(k_state_init, dim3((unsigned)((io.rows + 255) / 256)), dim3(256), 0, io))) return rc;
     return launch(k_state_records, dim3((unsigned)io.rows, (unsigned)k.parts), dim3(64), 0, k);
+  }
+  // sf_record_step / sf_record_flush: one of the record launches (k_record's mode)
+  int launch_record(const Record &k, int mode) {
+    SF_HIP(hipSetDevice(device));
+    return launch(k_record, dim3((unsigned)k.A), dim3(64), 0, k, mode);
+  }
+  // sf_record_collect_device: the outputs checked as sf_signals_step checks its own, then plan and copy
+  int launch_record_collect(const Record &k, uint8_t *d_bytes, int64_t max_bytes, int32_t *d_games, int32_t max_games, int64_t *d_counts) {
+    SF_HIP(hipSetDevice(device));
+    const char *who = "sf_record_collect_device";
+    int rc;
+    if ((rc = check_device_range(d_bytes, (size_t)max_bytes, 1, "d_bytes", who)) ||
+        (rc = check_device_range(d_games, (size_t)max_games * SF_RECORD_GAME_WORDS * sizeof(int32_t), 4, "d_games", who)) ||
+        (rc = check_device_range(d_counts, SF_RECORD_COUNT_WORDS * sizeof(int64_t), 8, "d_counts", who)))
+      return rc;
+    if ((rc = launch(k_record_plan, dim3(1), dim3(1024), 0, k, (long long)max_games, (long long)max_bytes, reinterpret_cast<long long *>(d_counts))))
+      return rc;
+    return launch(k_record_copy, dim3((unsigned)((k.A + 3) / 4)), dim3(256), 0, k, d_bytes, d_games);
   }
   bool can_rank() const { return true; }
   // k_rank runs right in front of the k_step launch it orders, inside that launch's pair of timing events: what
@@ -653,6 +761,9 @@ struct sf_snapshot {
 struct sf_signals {
   sf::Env<sf::HipRT>::SignalsObj *s;
 };
+struct sf_recorder {
+  sf::Env<sf::HipRT>::Recorder *r;
+};
 
 using sf::fail;  // SF_HIP in the entry points below
 
@@ -767,6 +878,43 @@ int sf_signals_step(sf_env *env, sf_signals *s, const sf_signals_io *io) {
 int sf_signals_status(sf_signals *s, int64_t out_host[4]) {
   if (!s) return sf::fail(SF_ERR_ARG, "null signals object");
   return s->s->owner->signals_status(s->s, out_host);
+}
+int sf_record_create(sf_env *env, int64_t bytes_per_arena, int32_t games_per_arena, sf_recorder **out) {
+  if (!out) return sf::fail(SF_ERR_ARG, "sf_record_create: null output handle");
+  *out = nullptr;
+  SF_ENV(env);
+  sf_recorder *h = new (std::nothrow) sf_recorder{nullptr};
+  if (!h) return sf::fail(SF_ERR_MEMORY, "host allocation failed");
+  if (int rc = env->e.record_create(bytes_per_arena, games_per_arena, &h->r)) {
+    delete h;
+    return rc;
+  }
+  *out = h;
+  return SF_OK;
+}
+int sf_record_destroy(sf_recorder *r) {
+  if (!r) return SF_OK;
+  const int rc = r->r->owner->record_destroy(r->r);
+  delete r;
+  return rc;
+}
+int sf_record_step(sf_env *env, sf_recorder *r, const uint8_t *d_cmd) {
+  SF_ENV(env);
+  return env->e.record_step(r ? r->r : nullptr, d_cmd);
+}
+int sf_record_flush(sf_env *env, sf_recorder *r) {
+  SF_ENV(env);
+  return env->e.record_flush(r ? r->r : nullptr);
+}
+int sf_record_collect_device(sf_recorder *r, uint8_t *d_bytes, int64_t max_bytes, int32_t *d_games, int32_t max_games,
+                             int64_t *d_counts) {
+  if (!r) return sf::fail(SF_ERR_ARG, "null recorder");
+  return r->r->owner->record_collect_device(r->r, d_bytes, max_bytes, d_games, max_games, d_counts);
+}
+int sf_record_collect(sf_recorder *r, uint8_t *bytes_host, int64_t max_bytes, int32_t *games_host, int32_t max_games,
+                      int64_t *counts_host) {
+  if (!r) return sf::fail(SF_ERR_ARG, "null recorder");
+  return r->r->owner->record_collect_host(r->r, bytes_host, max_bytes, games_host, max_games, counts_host);
 }
 int sf_step(sf_env *env, const uint8_t *cmd) {
   SF_ENV(env);

@@ -21,6 +21,7 @@
 #include "sf_obs.hpp"
 #include "sf_snapshot_blob.hpp"
 #include "sf_signals.hpp"
+#include "sf_record.hpp"
 #include "sf_state_records.hpp"
 
 namespace sf {
@@ -987,6 +988,113 @@ struct Env {
     if (int rc = rt.sync()) return rc;
     for (int i = 0; i < SIG_COUNTERS; ++i) out[i] = (int64_t)c[i];
     return SF_OK;
+  }
+
+  // ---- recording of games as command streams (sf_record_*; the lane functions are sf_record.hpp's, k_record*) ----------
+  struct Recorder {
+    Env *owner = nullptr;
+    Record k;                       // the kernels' struct: the environment's buffers and the recorder's own
+    int64_t *counts = nullptr;      // [SF_RECORD_COUNT_WORDS]: sf_record_collect's staging
+    uint8_t *out_bytes = nullptr;   // ... and its outputs, grown on demand
+    int32_t *out_games = nullptr;
+    int64_t out_bytes_n = 0, out_games_n = 0;
+  };
+  void record_release(Recorder *r) {
+    void *ptrs[] = {r->k.bytes, r->k.games, r->k.st, r->k.plan, r->counts, r->out_bytes, r->out_games};
+    for (void *q : ptrs)
+      if (q) rt.free(q);
+    delete r;
+  }
+  int record_create(int64_t bytes_per_arena, int32_t games_per_arena, Recorder **out) {
+    if (!out) return fail(SF_ERR_ARG, "sf_record_create: null output handle");
+    *out = nullptr;
+    if (bytes_per_arena < p.n_agents || bytes_per_arena >= ((int64_t)1 << 31))
+      return fail(SF_ERR_ARG, "sf_record_create: bytes_per_arena must be at least n_agents (one iteration) and below 2^31");
+    if (games_per_arena < 1 || (int64_t)games_per_arena * RG_WORDS >= ((int64_t)1 << 31))
+      return fail(SF_ERR_ARG, "sf_record_create: games_per_arena must be at least 1");
+    Recorder *r = new (std::nothrow) Recorder();
+    if (!r) return fail(SF_ERR_MEMORY, "host allocation failed");
+    r->owner = this;
+    memset(&r->k, 0, sizeof r->k);
+    const size_t A = (size_t)p.A;
+    int rc;
+    if ((rc = alloc(r->k.bytes, A * (size_t)bytes_per_arena)) || (rc = alloc(r->k.games, A * (size_t)games_per_arena * RG_WORDS)) ||
+        (rc = alloc(r->k.st, A * RC_WORDS)) || (rc = alloc(r->k.plan, A * RPL_WORDS)) || (rc = alloc(r->counts, (size_t)SF_RECORD_COUNT_WORDS))) {
+      record_release(r);
+      return rc;
+    }
+    r->k.hum = p.hum, r->k.scal = p.scal, r->k.results = p.results;
+    r->k.A = p.A, r->k.H = p.H, r->k.n_agents = p.n_agents, r->k.ind = p.ind, r->k.auto_reset = p.auto_reset;
+    r->k.G = games_per_arena, r->k.bpa = (int32_t)bytes_per_arena;
+    rt.zero(r->k.st, A * RC_WORDS * sizeof(int32_t));  // no open game, empty region and index
+    if ((rc = rt.sync())) {
+      record_release(r);
+      return rc;
+    }
+    *out = r;
+    return SF_OK;
+  }
+  int record_destroy(Recorder *r) {
+    if (!r) return SF_OK;
+    int rc = rt.sync();  // launches still in flight may read or write the regions
+    record_release(r);
+    return rc;
+  }
+  int record_usable(const Recorder *r, const char *who) const {
+    if (!r) return fail(SF_ERR_ARG, std::string(who) + ": null recorder");
+    if (r->owner != this) return fail(SF_ERR_ARG, std::string(who) + ": the recorder was created for another environment");
+    if (!was_reset) return fail(SF_ERR_STATE, std::string(who) + " before sf_reset");
+    if (int rc = not_mid_step(who)) return rc;
+    if (rp.status) return fail(SF_ERR_STATE, std::string(who) + " while a replay is loaded (sf_replay_load)");
+    return SF_OK;
+  }
+  // one iteration of every arena as the split step plays it, with the record launches around its halves: loop top ->
+  // first half -> the other players' lines -> second half (+ k_ep_late where sf_step_end launches it) -> closing; no host
+  // synchronisation
+  int record_step(Recorder *r, const uint8_t *d_cmds) {
+    if (int rc = record_usable(r, "sf_record_step")) return rc;
+    if (!d_cmds) return fail(SF_ERR_ARG, "sf_record_step: null command array");
+    Record k = r->k;
+    k.cmd = d_cmds;
+    int rc;
+    if ((rc = rt.launch_record(k, 0)) || (rc = rt.launch_step_half(p, NB, d_cmds, 1))) return rc;
+    if (p.n_agents > 1 && (rc = rt.launch_record(k, 1))) return rc;  // (a lone player has no other lines)
+    if ((rc = rt.launch_step_half(p, NB, d_cmds, 2)) || (rc = ep_late(false))) return rc;
+    return rt.launch_record(k, 2);
+  }
+  int record_flush(Recorder *r) {
+    if (int rc = record_usable(r, "sf_record_flush")) return rc;
+    return rt.launch_record(r->k, 3);
+  }
+  int record_collect_device(Recorder *r, uint8_t *d_bytes, int64_t max_bytes, int32_t *d_games, int32_t max_games, int64_t *d_counts) {
+    if (!r || !d_bytes || !d_games || !d_counts) return fail(SF_ERR_ARG, "sf_record_collect_device: null argument");
+    if (max_bytes < 1 || max_games < 1) return fail(SF_ERR_ARG, "sf_record_collect_device: max_bytes and max_games must be positive");
+    return rt.launch_record_collect(r->k, d_bytes, max_bytes, d_games, max_games, d_counts);
+  }
+  int record_collect_host(Recorder *r, uint8_t *bytes, int64_t max_bytes, int32_t *games, int32_t max_games, int64_t *counts) {
+    if (!r || !bytes || !games || !counts) return fail(SF_ERR_ARG, "sf_record_collect: null argument");
+    if (max_bytes < 1 || max_games < 1) return fail(SF_ERR_ARG, "sf_record_collect: max_bytes and max_games must be positive");
+    int rc;
+    if (r->out_bytes_n < max_bytes) {
+      if ((rc = rt.sync())) return rc;
+      if (r->out_bytes) rt.free(r->out_bytes);
+      r->out_bytes = nullptr, r->out_bytes_n = 0;
+      if ((rc = alloc(r->out_bytes, (size_t)max_bytes))) return rc;
+      r->out_bytes_n = max_bytes;
+    }
+    if (r->out_games_n < max_games) {
+      if ((rc = rt.sync())) return rc;
+      if (r->out_games) rt.free(r->out_games);
+      r->out_games = nullptr, r->out_games_n = 0;
+      if ((rc = alloc(r->out_games, (size_t)max_games * RG_WORDS))) return rc;
+      r->out_games_n = max_games;
+    }
+    if ((rc = rt.launch_record_collect(r->k, r->out_bytes, max_bytes, r->out_games, max_games, r->counts))) return rc;
+    rt.d2h(counts, r->counts, SF_RECORD_COUNT_WORDS * sizeof(int64_t));
+    if ((rc = rt.sync())) return rc;
+    if (counts[0] > 0) rt.d2h(games, r->out_games, (size_t)counts[0] * RG_WORDS * sizeof(int32_t));
+    if (counts[1] > 0) rt.d2h(bytes, r->out_bytes, (size_t)counts[1]);
+    return rt.sync();
   }
 
   // ---- parity tooling ----------------------------------------------------------------------------

@@ -78,6 +78,8 @@ def load_library():
             abi.bind_signals(L, "sf_")
         if hasattr(L, "sf_state_device"):  # (state records on the device; an older build loaded through SF_LIBRARY_PATH lacks them)
             abi.bind_state(L, "sf_")
+        if hasattr(L, "sf_record_create"):  # (recording of games; an older build loaded through SF_LIBRARY_PATH lacks it)
+            abi.bind_record(L, "sf_")
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -115,7 +117,8 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_step_begin", "sf_step_end", "sf_step_end_device", "sf_agent_alive", "sf_agent_alive_device", "sf_phase_draws",
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
            "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device",
-           "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS + abi.SIGNALS_EXPORTS + abi.STATE_EXPORTS]
+           "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS + abi.SIGNALS_EXPORTS + abi.STATE_EXPORTS +
+                                     abi.RECORD_EXPORTS]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -320,6 +323,79 @@ class Signals:
         return int(out[0]), int(out[1])
 
 
+def decode_games(games):
+    """Named arrays of the game records sf_record_collect* delivers (int32 [n][12]): arena, episode, tb (uint64), serial
+    (uint64), lines, iterations, end (abi.RECORD_*), outcome (int32 [n]) and offset (int64 [n], the stream's first byte in
+    the collected bytes)."""
+    r = np.ascontiguousarray(games, dtype=np.int32).reshape(-1, abi.RECORD_GAME_WORDS)
+    u = r.view(np.uint32).astype(np.uint64)
+    return {
+        "arena": r[:, 0].copy(), "episode": r[:, 1].copy(),
+        "tb": u[:, 2] | (u[:, 3] << np.uint64(32)), "serial": u[:, 4] | (u[:, 5] << np.uint64(32)),
+        "lines": r[:, 6].copy(), "iterations": r[:, 7].copy(), "end": r[:, 8].copy(), "outcome": r[:, 9].copy(),
+        "offset": (u[:, 10] | (u[:, 11] << np.uint64(32))).astype(np.int64),
+    }
+
+
+class Recorder:
+    """Games written out on the device as the command streams of `.sf_sample` files (strikeforce.h sf_record_*): step(d_cmd)
+    plays one iteration of every arena exactly as step_device(d_cmd, 1) does and appends the lines the reference's logger
+    would write; flush() closes every open game as cut; collect() hands out the closed games (int32 [n][12], see
+    decode_games) and their streams back to back (uint8), with the six counts by name; collect_device() does the same into
+    device buffers without a host synchronisation.  replay.samples_from_recording turns a collection into Samples.
+    Pointers are device addresses (int) or torch tensors.  close() before the environment's."""
+
+    def __init__(self, batch, bytes_per_arena, games_per_arena):
+        if not hasattr(batch.L, "sf_record_create"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_record_* entry points")
+        self.batch, self.L = batch, batch.L
+        self.bytes_per_arena, self.games_per_arena = int(bytes_per_arena), int(games_per_arena)
+        self.h = C.c_void_p()
+        rc = self.L.sf_record_create(batch.h, self.bytes_per_arena, self.games_per_arena, C.byref(self.h))
+        if rc != 0:
+            self.h = None
+            raise StrikeForceError("sf_record_create failed (%d): %s" % (rc, self.L.sf_last_error().decode()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.sf_record_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _ptr(x):
+        return x.data_ptr() if hasattr(x, "data_ptr") else x
+
+    def step(self, d_cmd_ptr):
+        self.batch._ck(self.L.sf_record_step(self.batch.h, self.h, self._ptr(d_cmd_ptr)), "sf_record_step")
+
+    def flush(self):
+        self.batch._ck(self.L.sf_record_flush(self.batch.h, self.h), "sf_record_flush")
+
+    def collect_device(self, d_bytes_ptr, max_bytes, d_games_ptr, max_games, d_counts_ptr):
+        self.batch._ck(self.L.sf_record_collect_device(self.h, self._ptr(d_bytes_ptr), int(max_bytes), self._ptr(d_games_ptr),
+                                                       int(max_games), self._ptr(d_counts_ptr)), "sf_record_collect_device")
+
+    def collect(self, max_bytes=None, max_games=None):
+        """(games int32 [n][12], bytes uint8 [m], counts dict) of the closed games that fit; synchronises.  The defaults
+        hold everything a recorder can hold."""
+        A = self.batch.cfg.arenas
+        max_bytes = int(max_bytes) if max_bytes is not None else A * self.bytes_per_arena
+        max_games = int(max_games) if max_games is not None else A * self.games_per_arena
+        data = np.zeros(max(max_bytes, 1), dtype=np.uint8)
+        games = np.zeros((max(max_games, 1), abi.RECORD_GAME_WORDS), dtype=np.int32)
+        counts = np.zeros(abi.RECORD_COUNT_WORDS, dtype=np.int64)
+        self.batch._ck(self.L.sf_record_collect(self.h, data.ctypes.data, max_bytes, games.ctypes.data, max_games,
+                                                counts.ctypes.data), "sf_record_collect")
+        named = dict(zip(abi.RECORD_COUNT_FIELDS, (int(x) for x in counts)))
+        return games[:named["games"]].copy(), data[:named["bytes"]].copy(), named
+
+
 class ArenaBatch:
     """A batch of independent arenas on one GPU.
 
@@ -383,6 +459,10 @@ class ArenaBatch:
     def signals(self):
         """Per-step vitals, deltas and a shaped reward on the device (sf_signals_create): see Signals."""
         return Signals(self)
+
+    def recorder(self, bytes_per_arena, games_per_arena):
+        """Games recorded on the device as `.sf_sample` command streams (sf_record_create): see Recorder."""
+        return Recorder(self, bytes_per_arena, games_per_arena)
 
     def state_device(self, io):
         """sf_state_device with a ready abi.StateIO: one or two stream-ordered launches, nothing else."""

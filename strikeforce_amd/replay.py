@@ -194,6 +194,50 @@ def match_workload_for(sample, rows, cols, map_bytes, portal=None, floors=1, H=6
     return config.Workload("replay-match", cfg, map_bytes, portal or [-1] * (floors * rows * cols))
 
 
+def _profile_tokens(p):
+    """The 32 integers of a character record from an abi.Profile (the inverse of abi.Profile.from_tokens)."""
+    t = [p.def_hp, p.mindamage_def, p.def_stamina, p.level_solo, p.level_timer, p.level_squad, p.money, p.rate_solo,
+         p.rate_timer, p.rate_squad, p.rate] + [p.cons[i] for i in range(4)]
+    for i in range(4):
+        t += [p.throw_lvl_cnt[i][0], p.throw_lvl_cnt[i][1]]
+    return [int(x) for x in t + [p.weapon_lvl[i] for i in range(8)] + [p.backpack_lvl]]
+
+
+def samples_from_recording(games, data, like):
+    """The games a Recorder collected (env.Recorder.collect: int32 [n][12] game records, the streams back to back) as
+    Samples, one per game in the order delivered: seed and command stream from the recording; `ind`, the teams, names and
+    character records — which the recorder does not know — from `like`, a Sample (a match the games continue or resemble)
+    or the workload the games were played on (Battle: one player per commanded human, the records of its configuration,
+    names p0, p1, ...; other modes: the one player's own lines, as the reference logs an offline game, so n_agents must be
+    1).  Each Sample carries the game's record as .recorded (arena, episode, iterations, end, outcome).  write_sample then
+    produces files the reference reads."""
+    from . import env
+    d = env.decode_games(games)
+    data = np.asarray(data, dtype=np.uint8)
+    if isinstance(like, Sample):
+        proto = dict(profile_tokens=like.profile_tokens, name=like.name, ind=like.ind, team=like.team, players=like.players,
+                     names=like.names, records=like.records, teams=like.teams, ip=like.ip, port=like.port, password=like.password)
+    else:
+        cfg = like.cfg
+        n = cfg.n_agents
+        if cfg.mode != abi.MODE_BATTLE and n != 1:
+            raise ValueError("only a Battle match logs other players' lines: pass a Sample to say who the players are")
+        recs = [_profile_tokens(cfg.agent_profile[i] if cfg.n_agent_profiles else cfg.player) for i in range(n)]
+        teams = [int(cfg.agent_team[i]) for i in range(n)] if n > 1 else [1]
+        proto = dict(profile_tokens=recs[cfg.ind], name="p%d" % cfg.ind, ind=cfg.ind, team=teams[cfg.ind], players=n,
+                     names=["p%d" % i for i in range(n)], records=recs, teams=teams)
+    out = []
+    for i in range(len(d["arena"])):
+        off, n = int(d["offset"][i]), int(d["lines"][i])
+        if off < 0 or off + n > len(data):
+            raise ValueError("game %d: its stream [%d, %d) lies outside the %d bytes given" % (i, off, off + n, len(data)))
+        s = Sample(int(d["tb"][i]), int(d["serial"][i]), commands=data[off:off + n].tobytes().decode("latin-1"), **proto)
+        s.recorded = dict(arena=int(d["arena"][i]), episode=int(d["episode"][i]), iterations=int(d["iterations"][i]),
+                          end=int(d["end"][i]), outcome=int(d["outcome"][i]))
+        out.append(s)
+    return out
+
+
 ReplayResult = collections.namedtuple("ReplayResult", "iterations state cursor")
 
 
