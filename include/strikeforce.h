@@ -344,6 +344,44 @@ typedef struct sf_signals_io {
 int sf_signals_step(sf_env *env, sf_signals *s, const sf_signals_io *io);
 int sf_signals_status(sf_signals *s, int64_t out_host[4]);   /* unresolved, rebased by detection, 0, 0; synchronises; clears */
 
+/* ---- action masks: which commands would do anything right now, on the device ----------------------------------------
+ * The reference's obey() (gameplay.hpp:695-821) silently drops most of what a bot may send: a step into a wall, a zombie
+ * or the map's edge, a shot with the bullet pool dry, 'u' with the selection on a weapon, '[' with no blocks left, a
+ * selection that is the selection already.  sf_action_mask_device says, for every (arena, commanded human) at once and
+ * without leaving the device, which commands are not such no-ops.
+ * The command table is valid_commands (gameplay.hpp:45) with '_' appended: SF_COMMANDS, SF_N_COMMANDS characters; bit k of
+ * a mask word stands for SF_COMMANDS[k].
+ * Definition.  For a commanded human g (slot g < n_agents) of arena a that is present (alive and commanded: SF_SIG_PRESENT's
+ * rule), bit k is set exactly when obey(SF_COMMANDS[k]) for that human, run on the arena's state as it is stored at the
+ * moment of the launch, would change at least one word of that state.  One exception: bit 0 ('+') is set for every present
+ * agent, so the word of a present agent is never 0.  An agent that is not present gets the word 0.  The one rule decides
+ * every corner: 'q' and 'e' are always set and '3' never; a selection that is the selection already is clear; 'x' that
+ * charges stamina but whose bullet may not enter the cell is set (the state changed), 'x' without enough stamina is clear;
+ * '_' is set while Hp != 0.  A present agent without a position (the value a Battle seat has before it is placed; no stored
+ * state holds it) gets bit 0 only.
+ * What a set bit is not: a promise.  The mask is taken from the stored state, and zombie_action, the bullets' half-tick and
+ * the humans earlier in the sweep run between that state and this human's obey (gameplay.hpp:1455-1464).  Nor does it say
+ * that a command is useful: a shot that charges stamina but cannot leave the muzzle stays set.  teleport and claim_chest
+ * follow obey and are not commands.
+ * One kernel launch in stream order on the environment's stream: no allocation, no copy, no host synchronisation; nothing
+ * of the environment is written; the struct and the action string travel in the kernel arguments (both may be temporaries)
+ * and the call may be captured in a graph behind sf_step_device.  Allowed whenever the state is stored: after any step,
+ * between sf_step_begin and sf_step_end, while a replay is loaded.
+ * SF_ERR_STATE: before the first sf_reset.  SF_ERR_ARG: null handles; no output at all; d_actions without action_string or
+ * the reverse; an action string that is empty, longer than 32 or holds a character that is not in SF_COMMANDS; a non-NULL
+ * output that is not device memory of the environment's device, is not 4-byte aligned or whose extent reaches past its
+ * allocation.  Nothing is launched then. */
+#define SF_COMMANDS "+qe3uzxawsdfghjkl;'cvbnm,./[]_"
+#define SF_N_COMMANDS 30
+typedef struct sf_action_mask_io {
+  uint32_t *d_commands;       /* optional out, device, [arenas][n_agents]: the 30-bit word, bit k = SF_COMMANDS[k] */
+  const char *action_string;  /* optional, host, 1..32 chars of SF_COMMANDS: a bot's action set ("+xzqeawsd"); repeats allowed */
+  uint32_t *d_actions;        /* optional out, device, [arenas][n_agents]: bit j = the bit of action_string[j]; what
+                                 sf_policy_act_masked takes as d_action_mask.  Needs action_string, and the reverse */
+} sf_action_mask_io;
+int sf_action_mask_device(sf_env *env, const sf_action_mask_io *io);
+int sf_action_mask(sf_env *env, uint32_t *out_host);   /* the command words [arenas][n_agents] through the host; synchronises */
+
 /* One iteration of gameplay::play()'s while(true) body, gameplay.hpp:1452-1471, followed by the next
  * iteration's loop-top (spawns + check_end, gameplay.hpp:1444-1450), for every arena.
  * cmd: host array [arenas][n_agents] of reference command chars (valid_commands gameplay.hpp:45, plus

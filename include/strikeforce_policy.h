@@ -109,6 +109,23 @@ int sf_policy_sparse_overflows(sf_policy *p, int32_t *count);
 int sf_policy_act(sf_policy *p, const float *d_probs, int32_t agents, const char *action_string, uint64_t seed,
                   int32_t greedy, uint8_t *d_cmd, int32_t *d_action);
 
+/* sf_policy_act under an action mask: the draw honours what sf_action_mask_device (strikeforce.h) says would do anything.
+ * d_action_mask: device uint32 per agent, bit j = action_string[j] is effective — sf_action_mask_io.d_actions for the same
+ * action string.  Per agent: v is scaled as in sf_policy_act (v[0] = 0.5, the rest scaled to 0.5 in all); every v[k] whose
+ * bit is clear becomes 0; bit 0 counts as set whatever the word says, so the word 0 of a dead seat yields action 0 ('+' in
+ * the bots' strings); then the same sum, the same hashed draw (greedy != 0: the arg-max, first maximum) and the same one-hot
+ * into action_input follow, and d_cmd, d_action and the policy's draw counter advance exactly as in sf_policy_act.  With
+ * every bit set the call is sf_policy_act bit for bit: command, action, memory, and the next call's draws.  A masked action
+ * is never drawn.
+ * d_probs_out (device, float32 [agents][9], may be NULL) receives v[k] / tot (IEEE division): the distribution the action was
+ * drawn from, which is what sf_rollout_record takes as d_probs.  A masked entry is exactly 0 there, so its log is -inf: a
+ * learner takes log-probabilities of the drawn action only (never masked), or masks the entropy term the same way.
+ * One launch on the policy's stream.  The fused sf_policy_predict_sparse keeps drawing unmasked: the masked closed loop is
+ * the forward (act = 0) + sf_action_mask_device + this call. */
+int sf_policy_act_masked(sf_policy *p, const float *d_probs, int32_t agents, const char *action_string, uint64_t seed,
+                         int32_t greedy, const uint32_t *d_action_mask /* sf_action_mask_io.d_actions */,
+                         uint8_t *d_cmd, int32_t *d_action /* may be NULL */, float *d_probs_out /* may be NULL, [agents][9] */);
+
 /* Agent::predict() + Agent::update() as the ONE call they are in the reference (Agent.hpp:200-222), for the closed loop
  * on the device: sf_policy_reset_memory + sf_policy_forward_sparse(_or_dense) + sf_policy_act in the forward's two
  * launches, with the same results bit for bit as the three calls in that order (tests/test_gpu_policy.py).

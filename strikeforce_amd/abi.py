@@ -196,6 +196,26 @@ def bind_signals(lib, prefix):
     return lib
 
 
+N_COMMANDS = 30  # SF_N_COMMANDS; SF_COMMANDS is ALL_COMMANDS: bit k of an action-mask word stands for ALL_COMMANDS[k]
+ACTION_MASK_EXPORTS = ("action_mask_device", "action_mask")
+
+
+class ActionMaskIO(C.Structure):
+    """sf_action_mask_io: the optional outputs of one sf_action_mask_device (device pointers as integers) and the host
+    string of the action set d_actions is laid out by."""
+    _fields_ = [("d_commands", C.c_void_p), ("action_string", C.c_char_p), ("d_actions", C.c_void_p)]
+
+
+def bind_action_mask(lib, prefix):
+    """Declare sf_action_mask_device / sf_action_mask (strikeforce.h) on a loaded library; handles and pointers as integers."""
+    g = lambda n: getattr(lib, prefix + n)
+    g("action_mask_device").argtypes = [C.c_void_p, C.POINTER(ActionMaskIO)]
+    g("action_mask").argtypes = [C.c_void_p, C.c_void_p]
+    for n in ACTION_MASK_EXPORTS:
+        g(n).restype = C.c_int
+    return lib
+
+
 STATE_COUNT_WORDS = 8  # SF_STATE_COUNT_WORDS
 STATE_COUNT_FIELDS = ("humans_alive", "zombies_alive", "bullets_alive", "portals_active",
                       "humans_extent", "zombies_extent", "bullets_extent", "portals_extent")

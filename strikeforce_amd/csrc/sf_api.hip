@@ -30,6 +30,7 @@
 #include "sf_obs_kernels.hpp"
 #include "sf_snapshot.hpp"
 #include "sf_signals.hpp"
+#include "sf_action_mask.hpp"
 #include "sf_record.hpp"
 #include "sf_host.hpp"
 // clang-format on
@@ -269,6 +270,10 @@ __global__ __launch_bounds__(256) void k_signals(Signals s) {
   signals_agent(s, i);
 }
 
+// sf_action_mask_device (sf_action_mask.hpp): one wavefront per arena and workgroup, as the step kernels have it; lanes
+// over (commanded human, direction) and over the slots of the entity tables.
+__global__ __launch_bounds__(64) void k_action_mask(ActionMask k) { ActionMaskCore<WaveGfx950>::body(k, (int)blockIdx.x); }
+
 // sf_state_device (sf_state_records.hpp): grid (rows, parts), one wavefront per workgroup as in k_snapshot; k_state_init
 // zeroes the count and digest rows the wavefronts of one row add into, in front of it on the same stream.
 __global__ __launch_bounds__(256) void k_state_init(sf_state_io io) {
@@ -477,6 +482,15 @@ struct HipRT {
     if (k.reward && (rc = check_device_range(k.reward, n * sizeof(float), 4, "d_reward", "sf_signals_step"))) return rc;
     if (k.rebase && (rc = check_device_range(k.rebase, n, 1, "d_rebase", "sf_signals_step"))) return rc;
     return launch(k_signals, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, k);
+  }
+  // sf_action_mask_device: one launch; the outputs are checked as sf_reset_arenas checks its own
+  int launch_action_mask(const ActionMask &k) {
+    SF_HIP(hipSetDevice(device));
+    const size_t bytes = (size_t)k.A * (size_t)k.n_agents * sizeof(uint32_t);
+    int rc;
+    if (k.commands && (rc = check_device_range(k.commands, bytes, 4, "d_commands", "sf_action_mask_device"))) return rc;
+    if (k.actions && (rc = check_device_range(k.actions, bytes, 4, "d_actions", "sf_action_mask_device"))) return rc;
+    return launch(k_action_mask, dim3((unsigned)k.A), dim3(64), 0, k);
   }
   // sf_state_device: the id list and every requested output checked as sf_signals_step checks its own, then k_state_init
   // (only with d_counts or d_digest) and k_state_records.  bytes: what each of the ten outputs must hold (Env::state_fill)
@@ -878,6 +892,14 @@ int sf_signals_step(sf_env *env, sf_signals *s, const sf_signals_io *io) {
 int sf_signals_status(sf_signals *s, int64_t out_host[4]) {
   if (!s) return sf::fail(SF_ERR_ARG, "null signals object");
   return s->s->owner->signals_status(s->s, out_host);
+}
+int sf_action_mask_device(sf_env *env, const sf_action_mask_io *io) {
+  SF_ENV(env);
+  return env->e.action_mask_device(io);
+}
+int sf_action_mask(sf_env *env, uint32_t *out_host) {
+  SF_ENV(env);
+  return env->e.action_mask_host(out_host);
 }
 int sf_record_create(sf_env *env, int64_t bytes_per_arena, int32_t games_per_arena, sf_recorder **out) {
   if (!out) return sf::fail(SF_ERR_ARG, "sf_record_create: null output handle");

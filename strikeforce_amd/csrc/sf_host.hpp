@@ -400,7 +400,7 @@ struct Env {
   void destroy() {
     void *ptrs[] = {d_logt, d_exptab, d_tab, d_map_flags, d_map_pidx, d_map_exits, p.hum, p.zom, p.bul, p.por, p.rng, p.rng2, p.scal, p.results,
                     p.flags, p.aux_dmg, p.aux_pidx, d_tb, d_serial, d_cmd, d_obs, d_nzprev, d_perm, tab.ep_ring, d_ep_cursor,
-                    d_ep_plan, d_ep_out, d_ep_counts, (void *)rp.streams, (void *)rp.off, rp.status, rp.taken};
+                    d_ep_plan, d_ep_out, d_ep_counts, (void *)rp.streams, (void *)rp.off, rp.status, rp.taken, d_amask};
     for (void *q : ptrs)
       if (q) rt.free(q);
     rt.shutdown();
@@ -988,6 +988,48 @@ struct Env {
     if (int rc = rt.sync()) return rc;
     for (int i = 0; i < SIG_COUNTERS; ++i) out[i] = (int64_t)c[i];
     return SF_OK;
+  }
+
+  // ---- action masks (sf_action_mask_*; the wavefront's body is sf_action_mask.hpp ActionMaskCore, k_action_mask) -------
+  // one stream-ordered launch; nothing is allocated, copied or waited for.  No not_mid_step(): the state is stored between
+  // the halves of a step too
+  int action_mask_device(const sf_action_mask_io *io) {
+    if (!io) return fail(SF_ERR_ARG, "sf_action_mask_device: null argument");
+    if (!was_reset) return fail(SF_ERR_STATE, "sf_action_mask_device before sf_reset");
+    if (!io->d_commands && !io->d_actions && !io->action_string) return fail(SF_ERR_ARG, "sf_action_mask_device: no output");
+    if (!io->d_actions != !io->action_string)
+      return fail(SF_ERR_ARG, "sf_action_mask_device: d_actions and action_string must both be given or both be NULL");
+    ActionMask k;
+    memset(&k, 0, sizeof k);
+    memset(k.action_bit, 31, sizeof k.action_bit);
+    if (io->action_string) {
+      const size_t n = strnlen(io->action_string, 33);
+      if (n < 1 || n > 32) return fail(SF_ERR_ARG, "sf_action_mask_device: action_string must hold 1..32 characters");
+      for (size_t j = 0; j < n; ++j) {
+        const char *at = strchr(SF_COMMANDS, io->action_string[j]);
+        if (!at) return fail(SF_ERR_ARG, "sf_action_mask_device: action_string holds a character that is not in SF_COMMANDS");
+        k.action_bit[j] = (uint8_t)(at - SF_COMMANDS);
+      }
+      k.n_actions = (int32_t)n;
+    }
+    k.hum = p.hum, k.zom = p.zom, k.bul = p.bul, k.por = p.por, k.scal = p.scal, k.flags = p.flags, k.tab = p.tab;
+    k.commands = io->d_commands, k.actions = io->d_actions;
+    k.A = p.A, k.F = p.F, k.N = p.N, k.M = p.M, k.cells_pad = p.cells_pad, k.H = p.H, k.Z = p.Z, k.B = p.B, k.P = p.P;
+    k.n_agents = p.n_agents, k.npc_block = p.npc_block;
+    return rt.launch_action_mask(k);
+  }
+  // the command words through the host: the launch into a buffer of the environment's own (allocated by the first call)
+  uint32_t *d_amask = nullptr;
+  int action_mask_host(uint32_t *out) {
+    if (!out) return fail(SF_ERR_ARG, "sf_action_mask: null output buffer");
+    if (!was_reset) return fail(SF_ERR_STATE, "sf_action_mask before sf_reset");
+    const size_t n = (size_t)p.A * (size_t)p.n_agents;
+    if (!d_amask)
+      if (int rc = alloc(d_amask, n)) return rc;
+    sf_action_mask_io io = {d_amask, nullptr, nullptr};
+    if (int rc = action_mask_device(&io)) return rc;
+    rt.d2h(out, d_amask, n * sizeof(uint32_t));
+    return rt.sync();
   }
 
   // ---- recording of games as command streams (sf_record_*; the lane functions are sf_record.hpp's, k_record*) ----------

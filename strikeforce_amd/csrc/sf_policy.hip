@@ -40,6 +40,7 @@
 #include "sf_policy_gemm.hpp"
 #include "sf_policy_stage.hpp"
 #include "sf_policy_tail.hpp"
+#include "sf_policy_mask.hpp"
 #include "sf_rollout.hpp"
 
 namespace sfp {
@@ -695,6 +696,22 @@ int sf_policy_act(sf_policy *pp, const float *d_probs, int32_t agents, const cha
   SFP_HIP(hipSetDevice(p->device));
   hipLaunchKernelGGL(sfp::k_act, dim3((unsigned)((agents + 255) / 256)), dim3(256), 0, p->stream, d_probs,
                      p->action_input, as, seed, p->draws++, greedy, d_cmd, d_action, agents);
+  SFP_HIP(hipGetLastError());
+  return SF_OK;
+}
+
+int sf_policy_act_masked(sf_policy *pp, const float *d_probs, int32_t agents, const char *action_string, uint64_t seed,
+                         int32_t greedy, const uint32_t *d_action_mask, uint8_t *d_cmd, int32_t *d_action, float *d_probs_out) {
+  Policy *p = reinterpret_cast<Policy *>(pp);
+  SFP_RC(sfp::check_kind(p, false, "sf_policy_act_masked"));
+  SFP_RC(sfp::check_agents(p, agents));
+  if (!d_probs || !d_cmd || !action_string || !d_action_mask) return sfp::fail(SF_ERR_ARG, "null buffer");
+  if (std::strlen(action_string) != (size_t)sfp::ACT) return sfp::fail(SF_ERR_ARG, "action_string must have 9 chars");
+  sfp::ActStr as;
+  std::memcpy(as.c, action_string, sfp::ACT);
+  SFP_HIP(hipSetDevice(p->device));
+  hipLaunchKernelGGL(sfp::k_act_masked, dim3((unsigned)((agents + 255) / 256)), dim3(256), 0, p->stream, d_probs, d_action_mask,
+                     p->action_input, as, seed, p->draws++, greedy, d_cmd, d_action, d_probs_out, agents);
   SFP_HIP(hipGetLastError());
   return SF_OK;
 }

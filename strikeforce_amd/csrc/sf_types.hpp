@@ -177,6 +177,23 @@ inline uint32_t snap_part_bytes(uint32_t row_bytes, int parts) {
 }
 inline uint32_t snap_width_for(uint32_t row_bytes) { return row_bytes % 16u == 0u ? 16u : row_bytes % 4u == 0u ? 4u : 2u; }
 
+// ---- action masks (sf_action_mask_device, sf_action_mask.hpp ActionMaskCore) ------------------------------------------
+// What k_action_mask takes, by value in the kernel arguments.  A struct of its own, like Signals and Snap: Params stays as
+// it is.  (Tables is declared above; the pointers are the environment's own.)
+struct ActionMask {
+  const uint32_t *hum;     // Params::hum  [HW_WORDS][A][H]
+  const uint32_t *zom;     // Params::zom  [ZW_WORDS][A][Z]
+  const uint32_t *bul;     // Params::bul  [BW_WORDS][A][B]
+  const uint32_t *por;     // Params::por  [A][P]
+  const int32_t *scal;     // Params::scal [A][SC_WORDS]
+  const uint8_t *flags;    // Params::flags [A][cells_pad]
+  const Tables *tab;       // Params::tab
+  uint32_t *commands;      // null, or [A][n_agents]: bit k = SF_COMMANDS[k]
+  uint32_t *actions;       // null, or [A][n_agents]: bit j = the bit of action_string[j]
+  int32_t A, F, N, M, cells_pad, H, Z, B, P, n_agents, npc_block, n_actions;
+  uint8_t action_bit[32];  // action_string[j]'s index in SF_COMMANDS; 31 (a bit no word has) behind the string's end
+};
+
 // ---- everything a kernel needs -----------------------------------------------------------------------
 struct Params {
   int32_t A, F, N, M, cells, cells_pad;

@@ -80,6 +80,8 @@ def load_library():
             abi.bind_state(L, "sf_")
         if hasattr(L, "sf_record_create"):  # (recording of games; an older build loaded through SF_LIBRARY_PATH lacks it)
             abi.bind_record(L, "sf_")
+        if hasattr(L, "sf_action_mask_device"):  # (action masks; an older build loaded through SF_LIBRARY_PATH lacks them)
+            abi.bind_action_mask(L, "sf_")
         L.sf_set_stream.argtypes = [vp, vp]
         L.sf_synchronize.argtypes = [vp]
         L.sf_kernel_time.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_int32)]
@@ -118,7 +120,7 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
            "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device",
            "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS + abi.SIGNALS_EXPORTS + abi.STATE_EXPORTS +
-                                     abi.RECORD_EXPORTS]
+                                     abi.RECORD_EXPORTS + abi.ACTION_MASK_EXPORTS]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -251,6 +253,16 @@ def decode_signals(vitals=None, delta=None):
                        (SIG_UNRESOLVED, "unresolved"), (SIG_IDLE, "idle")):
             out[n] = (out["flags"] & bit) != 0
     return out
+
+
+COMMANDS = abi.ALL_COMMANDS  # SF_COMMANDS: bit k of an action-mask word stands for COMMANDS[k]
+
+
+def decode_action_mask(words):
+    """Action-mask command words (host copies, uint32 [...]) as a bool array [..., 30]: [..., k] = COMMANDS[k] would do
+    something."""
+    w = np.asarray(words).astype(np.uint32)
+    return ((w[..., None] >> np.arange(abi.N_COMMANDS, dtype=np.uint32)) & np.uint32(1)).astype(bool)
 
 
 def decode_state(hdr=None, humans=None, zombies=None, bullets=None, portals=None, counts=None):
@@ -459,6 +471,39 @@ class ArenaBatch:
     def signals(self):
         """Per-step vitals, deltas and a shaped reward on the device (sf_signals_create): see Signals."""
         return Signals(self)
+
+    def action_mask_device(self, commands_ptr=None, action_string=None, actions_ptr=None):
+        """sf_action_mask_device on the caller's buffers: one stream-ordered launch, nothing else.  commands_ptr / actions_ptr:
+        device uint32 [arenas][n_agents]; actions_ptr needs action_string (1..32 characters of COMMANDS), and the reverse."""
+        if not hasattr(self.L, "sf_action_mask_device"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_action_mask_device")
+        io = abi.ActionMaskIO(commands_ptr, None if action_string is None else action_string.encode(), actions_ptr)
+        self._ck(self.L.sf_action_mask_device(self.h, C.byref(io)), "sf_action_mask_device")
+
+    def action_mask(self, action_string=None):
+        """Which commands would do anything right now, for every (arena, agent), on the device (sf_action_mask_device): bit k
+        of a word is set when obey(COMMANDS[k]) would change the stored state ('+' always, for a present agent; an absent
+        agent's word is 0).  -> an int32 tensor [arenas][n_agents] holding the bits of the unsigned words; with action_string
+        (a bot's action set, e.g. "+xzqeawsd") a pair: the command words and the action words, bit j = action_string[j] —
+        what PolicyBatch.act_masked takes.  The tensors are the batch's own, allocated once and rewritten by every call;
+        nothing is read on the host.  The mask is of the state as stored now: the zombies, the bullets and the humans
+        earlier in the sweep still move before this human's command is obeyed."""
+        import torch
+        own = self.__dict__.setdefault("_action_mask", {})
+        for key in ("commands", "actions"):
+            if key not in own and (key == "commands" or action_string is not None):
+                own[key] = torch.zeros((self.cfg.arenas, self.cfg.n_agents), dtype=torch.int32, device="cuda:%d" % self.cfg.device)
+        if action_string is None:
+            self.action_mask_device(own["commands"].data_ptr())
+            return own["commands"]
+        self.action_mask_device(own["commands"].data_ptr(), action_string, own["actions"].data_ptr())
+        return own["commands"], own["actions"]
+
+    def action_mask_host(self):
+        """The command words through the host (sf_action_mask): uint32 [arenas][n_agents]; synchronises."""
+        out = np.zeros((self.cfg.arenas, self.cfg.n_agents), dtype=np.uint32)
+        self._ck(self.L.sf_action_mask(self.h, out.ctypes.data_as(C.c_void_p)), "sf_action_mask")
+        return out
 
     def recorder(self, bytes_per_arena, games_per_arena):
         """Games recorded on the device as `.sf_sample` command streams (sf_record_create): see Recorder."""

@@ -201,6 +201,8 @@ def _bind(L):
     L.sf_policy_kernel_time_by_kernel.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     L.sf_policy_sparse_overflows.argtypes = [vp, C.POINTER(C.c_int32)]
     L.sf_policy_act.argtypes = [vp, vp, C.c_int32, C.c_char_p, C.c_uint64, C.c_int32, vp, vp]
+    if hasattr(L, "sf_policy_act_masked"):  # (an older build loaded through SF_LIBRARY_PATH lacks it)
+        L.sf_policy_act_masked.argtypes = [vp, vp, C.c_int32, C.c_char_p, C.c_uint64, C.c_int32, vp, vp, vp, vp]
     L.sf_policy_get_memory.argtypes = [vp, C.c_int32, _FP, _FP]
     L.sf_policy_set_memory.argtypes = [vp, C.c_int32, _FP, _FP]
     L.sf_policy_set_stream.argtypes = [vp, vp]
@@ -226,7 +228,7 @@ def _bind(L):
 # every symbol include/strikeforce_policy.h declares
 EXPORTS = ["sf_policy_create", "sf_policy_destroy", "sf_policy_reset_memory", "sf_policy_reset_memory_n", "sf_policy_forward", "sf_policy_forward_sparse",
            "sf_policy_forward_sparse_or_dense",
-           "sf_policy_sparse_overflows", "sf_policy_act", "sf_policy_predict_sparse",
+           "sf_policy_sparse_overflows", "sf_policy_act", "sf_policy_act_masked", "sf_policy_predict_sparse",
            "sf_policy_get_memory", "sf_policy_set_memory", "sf_policy_set_stream", "sf_policy_synchronize",
            "sf_policy_kernel_time", "sf_policy_kernel_time_ex", "sf_policy_kernel_time_by_kernel", "sf_policy_gemm", "sf_policy_gemm_split", "sf_policy_features", "sf_policy_abi_version",
            "sf_policy_update_actions", "sf_policy_load_weights", "sf_policy_weights_digest", "sf_policy_memory_rows"]
@@ -408,6 +410,21 @@ class PolicyBatch(_NetBatch):
         self._ck(self.L.sf_policy_act(self.h, C.c_void_p(d_probs_ptr), int(agents), action_string.encode(),
                                       C.c_uint64(seed), 1 if greedy else 0, C.c_void_p(d_cmd_ptr),
                                       C.c_void_p(d_action_ptr) if d_action_ptr else None), "sf_policy_act")
+
+    def act_masked(self, d_probs_ptr, agents, d_action_mask_ptr, d_cmd_ptr, seed=0, greedy=False, d_action_ptr=None,
+                   d_probs_out_ptr=None, action_string=ACTION_STRING):
+        """act() under an action mask (sf_policy_act_masked): d_action_mask_ptr is ArenaBatch.action_mask(action_string)'s
+        second tensor, uint32 per agent, bit j = action_string[j] would do something.  A masked action is never drawn; a
+        word of 0 (a dead seat) yields action 0.  d_probs_out_ptr: float32 [agents][9], the distribution the action was drawn
+        from (masked entries exactly 0: their log is -inf) — what the rollout buffer takes as d_probs.  With every bit set
+        this is act() bit for bit."""
+        if not hasattr(self.L, "sf_policy_act_masked"):
+            raise env.StrikeForceError("this build of libstrikeforce_amd.so has no sf_policy_act_masked")
+        opt = lambda x: C.c_void_p(x) if x else None
+        self._ck(self.L.sf_policy_act_masked(self.h, C.c_void_p(d_probs_ptr), int(agents), action_string.encode(),
+                                             C.c_uint64(seed), 1 if greedy else 0, C.c_void_p(d_action_mask_ptr),
+                                             C.c_void_p(d_cmd_ptr), opt(d_action_ptr), opt(d_probs_out_ptr)),
+                 "sf_policy_act_masked")
 
     def gemm(self, d_a_ptr, lda, d_w_ptr, d_bias_ptr, d_c_ptr, ldc, m, n, k):
         """The MFMA matrix kernel on its own: C = A W^T + bias on device buffers."""
