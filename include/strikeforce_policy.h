@@ -370,8 +370,61 @@ int sf_rollout_state(sf_rollout *r, int32_t t, const uint32_t **d_keys, const fl
 /* AgentModel::update_actions(one_hot(d_action[a])) (Agent.hpp:396, RewardNet.hpp:271-272) for agents [0, agents) of a
  * policy or a reward model; an index outside [0, 9) means 0, as in sf_reward_forward.  With it the stored rollout can be
  * replayed: a fresh agent always starts at slot 0, so sf_policy_reset_memory followed by rows 0..T-1 — forward on
- * the state of slot t, then this call on action[t] — reproduces every ready agent's sequence. */
+ * the state of slot t, then this call on action[t] — reproduces every ready agent's sequence.
+ * A block stored under the continuing rule (sf_rollout_continue) stays replayable: with the memory the agents had at slot 0
+ * restored, the following sequence reproduces every stored logp and value.  For each t: sf_policy_reset_memory_n(first[t]),
+ * then forward on sf_rollout_state(t), then this call on action[t].  The memory at slot 0 comes from resetting at the
+ * hand-over, as Agent.hpp:432 does, or from keeping it with sf_policy_memory_rows. */
 int sf_policy_update_actions(sf_policy *p, const int32_t *d_action, int32_t agents);
+
+/* ---- the rollout buffer across game ends: a [T][agents] block every T ticks, and GAE(lambda) over it ---------------------
+ * The per-game rule above is the reference Agent's; a learner that trains on fixed-length blocks wants every tick kept, the
+ * game ends inside a block marked, and returns that bootstrap from the state behind the last slot.
+ *
+ * sf_rollout_continue switches an sf_rollout to the continuing rule (d_first set: the caller's [T][agents] bytes, device)
+ * or back to the per-game rule (d_first NULL).  Stream-ordered, no synchronisation; it sets every cursor to 0.  Under the
+ * continuing rule sf_rollout_record does, per agent, in this order:
+ *   1. fill == T: the agent is ready.  Nothing is written, the tick is counted in `dropped`, as under the per-game rule.
+ *   2. otherwise the tick is appended at slot `fill`: everything the per-game rule stores, bit for bit, and
+ *      first[slot] = 1 if the agent's restart flag is set in this call (d_reset_mask, or d_reset_words / reset_stride /
+ *      reset_group; neither given: 0), else 0; then fill += 1.  A set restart flag never moves the cursor.
+ * sf_rollout_ready_device, sf_rollout_status, sf_rollout_release and sf_rollout_state work under both rules unchanged. */
+int sf_rollout_continue(sf_rollout *r, uint8_t *d_first);
+
+/* Returns, values and advantages of the READY agents (rows of the others are not touched), under either rule; under the
+ * per-game rule `first` counts as all zero.  Per agent, in f32, every product rounded before its add (no fused
+ * multiply-add), in slot order from T-1 down:
+ *   V_t   = the f32 log of value[t] when log_values is set (the reference's head, :401,407), else value[t]; V_T the same
+ *           of d_next_value
+ *   x_t   = reward_scale * reward[t]
+ *   end_t = first[t+1] for t < T-1; for t = T-1 the next tick's restart flag (d_next_mask, or d_next_words / next_stride /
+ *           next_group as in sf_rollout_step; both NULL: that tick continues the game)
+ *   G_t   = x_t                      if end_t is set, or if t = T-1 and d_next_value is NULL — the other term is ABSENT,
+ *                                    not a zero that is added
+ *         = gamma * boot_t + x_t     otherwise, with boot_{T-1} = V_T and for t < T-1
+ *           boot_t = G_{t+1} (lambda == 1), V_{t+1} (lambda == 0), else (1 - lambda) * V_{t+1} + lambda * G_{t+1} with
+ *           (1 - lambda) an f32 subtraction
+ *   d_returns = G, d_v = V, d_adv = G - V     ([T][agents] device arrays, each may be NULL, not all three)
+ * This is GAE(lambda): G_t - V_t = delta_t + gamma * lambda * (1 - end_t) * (G_{t+1} - V_{t+1}).  Skipping a term, where a
+ * product with an exact 0 or 1 would stand, keeps a reward of -inf or a log of 0 from turning its neighbours into NaN, and
+ * makes the reference a special case: lambda = 1, log_values = 1, reward_scale = 1.f - gamma (in f32), no next value and no
+ * game end give sf_rollout_returns' d_returns, d_logv and d_adv in every bit.
+ * A restart by sf_reset_arenas (a step limit) is a game end like any other: bootstrapping a cut game from its own last
+ * state is out of scope.
+ * Two launches — V, fully parallel; then the recursion, one lane per agent — on the rollout's stream, no synchronisation.
+ * With d_v NULL and log_values set, V goes to a [T][agents] array of the library's, allocated by the first such call.
+ * SF_ERR_ARG: gamma or lambda outside [0, 1] or NaN; both d_next_mask and d_next_words given; next_stride or next_group
+ * below 1 with d_next_words; every output NULL. */
+typedef struct sf_rollout_gae_io {
+  float gamma, lambda, reward_scale;
+  int32_t log_values;
+  const float *d_next_value;
+  const uint8_t *d_next_mask;
+  const int32_t *d_next_words;
+  int32_t next_stride, next_group;
+  float *d_returns, *d_v, *d_adv;
+} sf_rollout_gae_io;
+int sf_rollout_gae(sf_rollout *r, const sf_rollout_gae_io *io);
 
 /* ---- parameters in: what a learner hands back ---------------------------------------------------------------------------
  * The parameters the next forward sees are these (optimizer->step(), bots/bot-1/Agent.hpp:415-417, then model->forward,

@@ -42,6 +42,7 @@
 #include "sf_policy_tail.hpp"
 #include "sf_policy_mask.hpp"
 #include "sf_rollout.hpp"
+#include "sf_rollout_gae.hpp"
 
 namespace sfp {
 
@@ -824,7 +825,10 @@ struct Rollout {
   int device = 0, agents = 0;
   hipStream_t stream = nullptr;
   RolloutDst d{};
+  uint8_t *first = nullptr;  // the caller's [T][agents], set: the continuing rule (sf_rollout_continue)
+  float *v = nullptr;        // [T][agents], sf_rollout_gae's V when the caller takes none; made by the first call that needs it
   ~Rollout() {
+    if (v) (void)hipFree(v);
     if (d.fill) (void)hipFree(d.fill);
     if (d.counters) (void)hipFree(d.counters);
   }
@@ -902,8 +906,57 @@ int sf_rollout_record(sf_rollout *rr, const sf_rollout_step *io) {
   s.reset_group = io->reset_group > 0 ? io->reset_group : 1;
   s.agents = io->agents;
   SFP_HIP(hipSetDevice(r->device));
-  hipLaunchKernelGGL(sfp::k_rollout_record, dim3((unsigned)((io->agents + 3) / 4)), dim3(256), 0, r->stream, r->d, s);
+  const dim3 grid((unsigned)((io->agents + 3) / 4));
+  if (r->first)
+    hipLaunchKernelGGL(sfp::k_rollout_record_cont, grid, dim3(256), 0, r->stream, r->d, s, r->first);
+  else
+    hipLaunchKernelGGL(sfp::k_rollout_record, grid, dim3(256), 0, r->stream, r->d, s);
   SFP_HIP(hipGetLastError());
+  return SF_OK;
+}
+
+int sf_rollout_continue(sf_rollout *rr, uint8_t *d_first) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r) return sfp::fail(SF_ERR_ARG, "null rollout");
+  SFP_HIP(hipSetDevice(r->device));
+  SFP_HIP(hipMemsetAsync(r->d.fill, 0, (size_t)r->agents * sizeof(int32_t), r->stream));
+  r->first = d_first;
+  return SF_OK;
+}
+
+int sf_rollout_gae(sf_rollout *rr, const sf_rollout_gae_io *io) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!r || !io) return sfp::fail(SF_ERR_ARG, "null rollout or io");
+  if (!(io->gamma >= 0.f && io->gamma <= 1.f) || !(io->lambda >= 0.f && io->lambda <= 1.f))
+    return sfp::fail(SF_ERR_ARG, "gamma and lambda must lie in [0, 1]");
+  if (io->d_next_mask && io->d_next_words) return sfp::fail(SF_ERR_ARG, "the next tick's restart flags: d_next_mask or d_next_words, not both");
+  SFP_RC(sfp::check_resets(io->d_next_words, io->next_stride, io->next_group));
+  if (!io->d_returns && !io->d_v && !io->d_adv) return sfp::fail(SF_ERR_ARG, "null buffer");
+  SFP_HIP(hipSetDevice(r->device));
+  const sfp::RolloutDst &d = r->d;
+  // V: the stored values themselves when nobody asks for a copy or a logarithm of them
+  const float *v = d.value;
+  if (io->log_values || io->d_v) {
+    float *out = io->d_v;
+    if (!out) {
+      if (!r->v && hipMalloc(reinterpret_cast<void **>(&r->v), (size_t)d.T * (size_t)r->agents * sizeof(float)) != hipSuccess)
+        return sfp::fail(SF_ERR_MEMORY, "hipMalloc failed (sf_rollout_gae's V)");
+      out = r->v;
+    }
+    const dim3 grid((unsigned)((r->agents + 255) / 256), (unsigned)((d.T + sfp::GV_ROWS - 1) / sfp::GV_ROWS));
+    hipLaunchKernelGGL(sfp::k_rollout_gae_v, grid, dim3(256), 0, r->stream, d.fill, d.value, out, d.T, d.stride, io->log_values ? 1 : 0, r->agents);
+    SFP_HIP(hipGetLastError());
+    v = out;
+  }
+  if (io->d_returns || io->d_adv) {
+    sfp::GaeArgs g{};
+    g.gamma = io->gamma, g.lambda = io->lambda, g.scale = io->reward_scale, g.log_values = io->log_values ? 1 : 0;
+    g.next_value = io->d_next_value, g.next_mask = io->d_next_mask, g.next_words = io->d_next_words;
+    g.next_stride = io->next_stride, g.next_group = io->next_group > 0 ? io->next_group : 1;
+    g.first = r->first, g.v = v, g.returns = io->d_returns, g.adv = io->d_adv, g.agents = r->agents;
+    hipLaunchKernelGGL(sfp::k_rollout_gae, dim3((unsigned)((r->agents + 63) / 64)), dim3(64), 0, r->stream, d, g);
+    SFP_HIP(hipGetLastError());
+  }
   return SF_OK;
 }
 

@@ -6,6 +6,11 @@ One reference `Agent` keeps `states, log_probs, values, rewards, actions` per ga
 ``RewardBatch.reward_sparse``: it allocates the storage as torch tensors (slot-major, ``[T][agents]...``, exposed as
 attributes), records one tick per call, and hands the learner returns, log V, advantages and the statistics of the agents
 whose buffer is full.  The learners themselves (gradients, AdamW, backups) are the caller's.  No CPU path.
+
+That is the reference's rule, one buffer per game: a restart rewinds the agent to slot 0.  ``RolloutBatch(...,
+continuing=True)`` is the buffer of a learner that trains on fixed blocks instead (sf_rollout_continue): every tick is kept,
+a restart is stored in ``first`` and never moves the cursor, and ``gae()`` (sf_rollout_gae) computes GAE(lambda) returns,
+values and advantages over a full block, bootstrapped from the value of the state behind it, game ends cutting the recursion.
 """
 import ctypes as C
 
@@ -16,7 +21,7 @@ HIDDEN, ACTIONS = policy.HIDDEN, policy.ACTIONS
 # every sf_rollout_* symbol include/strikeforce_policy.h declares (sf_policy_update_actions is in policy.EXPORTS)
 EXPORTS = ["sf_rollout_create", "sf_rollout_destroy", "sf_rollout_set_stream", "sf_rollout_synchronize", "sf_rollout_record",
            "sf_rollout_fill_device", "sf_rollout_ready_device", "sf_rollout_status", "sf_rollout_returns", "sf_rollout_release",
-           "sf_rollout_state"]
+           "sf_rollout_state", "sf_rollout_continue", "sf_rollout_gae"]
 
 
 class Buffers(C.Structure):
@@ -31,6 +36,13 @@ class Step(C.Structure):
                 ("agents", C.c_int32), ("d_probs", C.c_void_p), ("d_value", C.c_void_p), ("d_action", C.c_void_p),
                 ("d_reward", C.c_void_p), ("d_disc", C.c_void_p), ("d_imitate", C.c_void_p), ("d_reset_mask", C.c_void_p),
                 ("d_reset_words", C.c_void_p), ("reset_stride", C.c_int32), ("reset_group", C.c_int32)]
+
+
+class GaeIO(C.Structure):
+    """sf_rollout_gae_io."""
+    _fields_ = [("gamma", C.c_float), ("lam", C.c_float), ("reward_scale", C.c_float), ("log_values", C.c_int32),
+                ("d_next_value", C.c_void_p), ("d_next_mask", C.c_void_p), ("d_next_words", C.c_void_p), ("next_stride", C.c_int32),
+                ("next_group", C.c_int32), ("d_returns", C.c_void_p), ("d_v", C.c_void_p), ("d_adv", C.c_void_p)]
 
 
 def _bind(L):
@@ -49,8 +61,11 @@ def _bind(L):
     L.sf_rollout_returns.argtypes = [vp, C.c_float, vp, vp, vp, vp]
     L.sf_rollout_release.argtypes = [vp, vp]
     L.sf_rollout_state.argtypes = [vp, C.c_int32, pp, pp, pp, pp, C.POINTER(C.c_int32)]
+    if hasattr(L, "sf_rollout_gae"):  # (an older build loaded through SF_LIBRARY_PATH lacks them)
+        L.sf_rollout_continue.argtypes = [vp, vp]
+        L.sf_rollout_gae.argtypes = [vp, C.POINTER(GaeIO)]
     for n in EXPORTS:
-        if n != "sf_rollout_destroy":
+        if n != "sf_rollout_destroy" and hasattr(L, n):
             getattr(L, n).restype = C.c_int
     L._sf_rollout_bound = True
 
@@ -59,9 +74,10 @@ class RolloutBatch:
     """The five vectors of `agents` reference Agents, T slots each.  Tensors (device, slot-major): keys, vals
     [T][agents][list_cap], counts [T][agents], pov [T][agents][160] (None with store_states=False), action [T][agents]
     int32, logp [T][agents][9], value, reward [T][agents], disc [T][agents] and imitate [T][agents] uint8 (None unless
-    asked for)."""
+    asked for).  continuing=True: the buffer spans game ends (sf_rollout_continue) — a restart flag never rewinds an agent,
+    it is stored in `first` [T][agents] uint8, and every T ticks all agents that recorded every tick are ready."""
 
-    def __init__(self, agents, T, list_cap, store_states=True, store_disc=False, store_imitate=False, device=0):
+    def __init__(self, agents, T, list_cap, store_states=True, store_disc=False, store_imitate=False, device=0, continuing=False):
         import torch
         self.L = env.load_library()
         if not hasattr(self.L, "sf_rollout_create"):
@@ -80,10 +96,11 @@ class RolloutBatch:
             self.action, self.logp, self.value, self.reward = new((), i32), new((ACTIONS,), f32), new((), f32), new((), f32)
             self.disc = new((), f32) if store_disc else None
             self.imitate = new((), torch.uint8) if store_imitate else None
+            self.first = new((), torch.uint8) if continuing else None
             ptr = lambda t: t.data_ptr() if t is not None else None
         else:  # (no device, or sizes no tensor can have: the library says which — SF_ERR_DEVICE / SF_ERR_ARG)
             self.keys = self.vals = self.counts = self.pov = self.disc = self.imitate = None
-            self.action = self.logp = self.value = self.reward = None
+            self.action = self.logp = self.value = self.reward = self.first = None
             ptr, dev = (lambda t: None), None
         b = Buffers(ptr(self.keys), ptr(self.vals), ptr(self.counts), ptr(self.pov), ptr(self.action), ptr(self.logp), ptr(self.value),
                     ptr(self.reward), ptr(self.disc), ptr(self.imitate))
@@ -93,6 +110,10 @@ class RolloutBatch:
             raise env.StrikeForceError("sf_rollout_create failed (%d): %s" % (rc, self.L.sf_last_error().decode()))
         self.h = h
         self._torch, self._dev = torch, dev
+        if continuing:
+            if not hasattr(self.L, "sf_rollout_continue"):
+                raise env.StrikeForceError("this build of libstrikeforce_amd.so has no sf_rollout_continue")
+            self._ck(self.L.sf_rollout_continue(self.h, C.c_void_p(self.first.data_ptr())), "sf_rollout_continue")
 
     def _ck(self, rc, what):
         if rc != 0:
@@ -160,6 +181,27 @@ class RolloutBatch:
             out = (nan((self.T, self.agents)), nan((self.T, self.agents)), nan((self.T, self.agents)), nan((self.agents, 4)))
         self._ck(self.L.sf_rollout_returns(self.h, C.c_float(gamma), *[C.c_void_p(x.data_ptr()) if x is not None else None for x in out]),
                  "sf_rollout_returns")
+        return out
+
+    def gae(self, gamma, lam, reward_scale=1.0, log_values=False, next_value=None, next_mask=None, next_words=None, out=None):
+        """GAE(lambda) over the ready agents' buffers (sf_rollout_gae): (returns, v, adv), [T][agents] each; game ends inside
+        the buffer (`first`) cut the recursion.  next_value: device float32 per agent (a tensor or its address), the value
+        head's output for the state behind slot T - 1, None: no bootstrap; next_mask (uint8 per agent) or next_words
+        (ArenaBatch.done_view_device()'s triple): that tick's restart flags.  log_values: V is the f32 log of the stored
+        value, as the reference's head has it.  out: three tensors, each may be None.  Rows of agents that are not ready
+        are not written (new tensors hold NaN there)."""
+        t = self._torch
+        if out is None:
+            nan = lambda: t.full((self.T, self.agents), float("nan"), dtype=t.float32, device=self._dev)
+            out = (nan(), nan(), nan())
+        ptr = lambda x: None if x is None else C.c_void_p(x if isinstance(x, int) else x.data_ptr())
+        io = GaeIO()
+        io.gamma, io.lam, io.reward_scale, io.log_values = gamma, lam, reward_scale, 1 if log_values else 0
+        io.d_next_value, io.d_next_mask = ptr(next_value), ptr(next_mask)
+        if next_words is not None:
+            io.d_next_words, io.next_stride, io.next_group = next_words
+        io.d_returns, io.d_v, io.d_adv = (ptr(x) for x in out)
+        self._ck(self.L.sf_rollout_gae(self.h, C.byref(io)), "sf_rollout_gae")
         return out
 
     def release(self, mask=None):
