@@ -685,6 +685,82 @@ typedef struct sf_state_io {
 int sf_state_device(sf_env *env, const sf_state_io *io);
 int sf_state_bytes(sf_env *env, const sf_state_io *io, int64_t bytes_out[10]);
 
+/* ---- write arenas from state records, on the device --------------------------------------------------------------------
+ * The inverse of sf_state_device.  The reference can set a world up in one way only, replaying a logged game from tick 0
+ * (gameplay.hpp:968-986); sf_reset builds one from a seed and sf_snapshot_load reloads an opaque state of this library.
+ * sf_state_put_device packs the canonical records — a state the caller designed, edited, or took from sf_state_device,
+ * sf_dump_arena or the oracle's dump — into the arenas a row map names, in stream order, from device buffers the caller
+ * owns.  Arena a takes row d_row_of_arena[a]; many arenas may name one row (the fork); -1: no word of the arena is written.
+ *   The core property.  Take an environment B of the same configuration as A and put into arena y of B everything
+ *     sf_state_device wrote for arena x of A (whole pools, all three cell tables).  Then y of B cannot be told from x of A by
+ *     any reader or any later step: all ten outputs of sf_state_device and sf_state_digest are equal; observations, action
+ *     masks, sf_done* and the results of later games are equal; under equal commands the digest after every later step is
+ *     equal, across game ends under auto_reset too.
+ *   What the destination keeps, by sf_snapshot_load's rule: sf_arena_hdr.episodes (the record's value is ignored), the
+ *     result latch, the episode-log ring and its cursor, the cursors of replays, rollout buffers and networks.  The per-step
+ *     restart flag of a written arena (what sf_done reports under auto_reset) is cleared and sf_phase_draws of it is 0
+ *     until its next step.  The put is announced through d_selected as sf_reset_arenas announces a restart; pass it as
+ *     sf_signals_step's d_rebase, to sf_policy_reset_memory and to sf_rollout_record.  The signals' rule 1 and the recorder
+ *     (BROKEN) detect a loaded arena on their own as they detect sf_snapshot_load: neither needed a change.
+ *   State the records do not show is derived: which humans are commanded, which occupy their cell and which agent record
+ *     they were built from (from the slot, the configuration and `alive`: a dead `ind` keeps its cell and its command, every
+ *     other dead human loses both); the generator's seed digits (the decimal digits of hdr.serial and hdr.tb); the next
+ *     episode's generator under auto_reset, armed as after a restart with the seed hdr.tb + reseed_stride (the restart
+ *     that adopts it draws whatever is missing: the trajectory is the one of an arena that warmed it up on the way); the
+ *     draw count jomle - 1042, the population the launch order uses and the words of the large pools in use.  Slots that
+ *     are not alive / active are written in one form: all-zero words, a human slot never used (way 0) as sf_reset leaves it.
+ *   Parts.  Every part is optional: with d_hdr NULL the scalars, the seeds and both generators stay; a table that is NULL
+ *     stays, with its derived scalars (the population only changes when humans and zombies are both given); the three cell
+ *     tables come all or none.  A table that is given is written over its whole pool: humans / zombies / bullets / portals
+ *     say how many slots per row the caller's table holds, 0 .. the cap, and the slots behind the cut become empty.
+ *   Validation, per row, before any word of any arena is written.  No field becomes an address or a table index
+ *     unchecked: every placed position inside floors x rows x cols; way 1..4 (a human's 0 only on an all-zero slot); the
+ *     0 / 1 fields; team 0..255; vec -1..2, ind -1..14 and, where vec selects a table, inside it (consumables and
+ *     throwables 4, weapons 8); item counts 0..65535, blocks / portals 0..255, portal_ind -1..cap_portals-1 (254 at most);
+ *     a bullet's owner 0..cap_humans, range / traveled 0..65535, effect an int16; generator words 0..65536, jomle 1042 ..
+ *     2^32-1, frame and steps 0..2^31-1, the counters int32 values, done 0 / 1, outcome 0..6; the consumable type of a cell
+ *     only under SF_CELL_CHEST, cell_dmg 0 off a player-built cell, cell_portal -1 off an entrance, in [0, cap_portals) on a
+ *     player-built entrance and the map's own number on a map entrance.  A row that fails writes nothing to any arena that
+ *     names it: d_status has the SF_PUT_BAD_* bits of its failed parts and the library counts the arena as refused.  A row
+ *     index outside [-1, rows) never becomes an address: SF_PUT_BAD_ROW, counted apart.
+ *     Consistency of the game is the caller's: two occupants of one cell, an occupant in a wall, a `ref` bit that
+ *     disagrees with its neighbours are played as they stand; the guarantees for those are memory safety and determinism.
+ *   d_status, int32 [arenas]: -1 not named, 0 written, > 0 refused.  d_selected, uint8 [arenas][n_agents]: 1 for every
+ *     agent of an arena that was written, else 0.  sf_state_put_status: arenas written, refused, named a row out of range,
+ *     0, since the last call; it synchronises and clears.
+ * Three launches on the environment's stream (the verdict rows zeroed, the check over the rows, the write over the
+ * arenas), no copy and no host synchronisation; the struct travels in the kernel arguments and the call may be captured
+ * in a graph.  The verdict rows (32 bytes a row) are the library's, allocated by the first call that needs more rows than
+ * any call before it (outside a capture); later calls allocate nothing.
+ * sf_load_arena is the host mirror of sf_dump_arena: whole pools from host memory, any of them NULL (the cell tables all
+ * or none), through the same launches; it synchronises, and a refused state is SF_ERR_ARG with the reason in sf_last_error.
+ * SF_ERR_STATE: before the first sf_reset, between sf_step_begin and sf_step_end, while a replay is loaded, on a runtime
+ * without the launches.  SF_ERR_ARG: null handles or a null d_row_of_arena, rows < 1, a cut below 0 or above its cap, every
+ * part NULL, one or two of the three cell tables, a pointer that is not device memory of the environment's device, is not
+ * aligned (8 bytes d_hdr, 1 d_cell_flags and d_selected, 4 the others) or whose extent reaches past its allocation;
+ * nothing is launched then. */
+enum { SF_PUT_BAD_HDR = 1, SF_PUT_BAD_HUMAN = 2, SF_PUT_BAD_ZOMBIE = 4, SF_PUT_BAD_BULLET = 8, SF_PUT_BAD_PORTAL = 16,
+       SF_PUT_BAD_CELL = 32, SF_PUT_BAD_ROW = 64 };
+typedef struct sf_state_put_io {
+  const int32_t *d_row_of_arena; /* device int32 [arenas]: arena a takes row d_row_of_arena[a]; -1: no word of it is written */
+  int32_t rows;
+  int32_t humans, zombies, bullets, portals; /* slots per row in the four tables, 0 .. cap; slots behind the cut become empty */
+  const sf_arena_hdr *d_hdr;        /* each part optional, [rows]; NULL: that part of the destination stays as it is */
+  const sf_human_rec *d_humans;     /* [rows][humans]  */
+  const sf_zombie_rec *d_zombies;   /* [rows][zombies] */
+  const sf_bullet_rec *d_bullets;   /* [rows][bullets] */
+  const sf_portal_rec *d_portals;   /* [rows][portals] */
+  const uint8_t *d_cell_flags;      /* the three cell tables: all or none; [rows][floors*rows*cols] */
+  const int32_t *d_cell_dmg, *d_cell_portal;
+  int32_t *d_status;                /* optional out, [arenas] */
+  uint8_t *d_selected;              /* optional out, [arenas][n_agents] */
+} sf_state_put_io;
+int sf_state_put_device(sf_env *env, const sf_state_put_io *io);
+int sf_state_put_status(sf_env *env, int64_t out_host[4]);
+int sf_load_arena(sf_env *env, int32_t arena, const sf_arena_hdr *hdr, const sf_human_rec *humans, const sf_zombie_rec *zombies,
+                  const sf_bullet_rec *bullets, const sf_portal_rec *portals, const uint8_t *cell_flags, const int32_t *cell_dmg,
+                  const int32_t *cell_portal);
+
 /* Stream control: the library launches on this hipStream_t (passed as void*); NULL = default stream. */
 int sf_set_stream(sf_env *env, void *hip_stream);
 int sf_synchronize(sf_env *env);

@@ -241,6 +241,32 @@ def bind_state(lib, prefix):
     return lib
 
 
+PUT_BAD_HDR, PUT_BAD_HUMAN, PUT_BAD_ZOMBIE, PUT_BAD_BULLET, PUT_BAD_PORTAL, PUT_BAD_CELL, PUT_BAD_ROW = 1, 2, 4, 8, 16, 32, 64  # SF_PUT_BAD_*
+STATE_PUT_PARTS = ("d_hdr", "d_humans", "d_zombies", "d_bullets", "d_portals", "d_cell_flags", "d_cell_dmg", "d_cell_portal")
+STATE_PUT_STATUS_FIELDS = ("written", "refused", "row_out_of_range", "reserved")  # sf_state_put_status
+STATE_PUT_EXPORTS = ("state_put_device", "state_put_status", "load_arena")
+
+
+class StatePutIO(C.Structure):
+    """sf_state_put_io: the row map, the cuts, the optional parts and the two optional outputs of one sf_state_put_device
+    (device pointers as integers)."""
+    _fields_ = [("d_row_of_arena", C.c_void_p), ("rows", C.c_int32),
+                ("humans", C.c_int32), ("zombies", C.c_int32), ("bullets", C.c_int32), ("portals", C.c_int32)] + [
+        (n, C.c_void_p) for n in STATE_PUT_PARTS] + [("d_status", C.c_void_p), ("d_selected", C.c_void_p)]
+
+
+def bind_state_put(lib, prefix):
+    """Declare sf_state_put_device / sf_state_put_status / sf_load_arena (strikeforce.h) on a loaded library."""
+    g = lambda n: getattr(lib, prefix + n)
+    vp = C.c_void_p
+    g("state_put_device").argtypes = [vp, C.POINTER(StatePutIO)]
+    g("state_put_status").argtypes = [vp, C.POINTER(C.c_int64 * 4)]
+    g("load_arena").argtypes = [vp, C.c_int32] + [vp] * 8
+    for n in STATE_PUT_EXPORTS:
+        g(n).restype = C.c_int
+    return lib
+
+
 RECORD_GAME_WORDS, RECORD_COUNT_WORDS = 12, 6  # SF_RECORD_GAME_WORDS, SF_RECORD_COUNT_WORDS
 RECORD_GAME_ENDED, RECORD_CUT, RECORD_OVERFLOW, RECORD_BROKEN = 1, 2, 3, 4  # SF_RECORD_*
 RECORD_COUNT_FIELDS = ("games", "bytes", "games_pending", "bytes_pending", "games_lost", "bytes_substituted")

@@ -7,6 +7,7 @@
 //   k_snapshot<SAVE>, the copy between the state buffers and a snapshot object (sf_snapshot.hpp)
 //   k_signals, vitals / delta / reward per (arena, agent) behind a step (sf_signals.hpp)
 //   k_state_init / k_state_records, every arena's canonical records, counts and digest (sf_state_records.hpp)
+//   k_put_init / k_put_check / k_put_write, arenas written from such records (sf_state_put.hpp)
 //   k_record, k_record_plan / k_record_copy, games written out as command streams and their collection (sf_record.hpp)
 //   HipRT, the runtime Env<RT> (sf_host.hpp) launches through
 //   Comm, the RCCL exchange of the multi-GPU path
@@ -284,6 +285,20 @@ __global__ __launch_bounds__(64) void k_state_records(StateRec s) {
   state_records_body(s, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+// sf_state_put_device (sf_state_put.hpp): k_put_init zeroes the rows' verdicts, k_put_check — grid (rows, parts),
+// one wavefront per workgroup — ORs the reason bits and takes counts and extents, k_put_write — grid (arenas, parts) —
+// reads the verdict of the arena's row first and packs the records of rows that passed.
+__global__ __launch_bounds__(256) void k_put_init(StatePut s) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i < s.io.rows) put_init_body(s, i);
+}
+__global__ __launch_bounds__(64) void k_put_check(StatePut s) {
+  state_put_check_body(s, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y);
+}
+__global__ __launch_bounds__(64) void k_put_write(StatePut s) {
+  state_put_write_body(s, (int)blockIdx.x, (int)blockIdx.y, (int)gridDim.y);
+}
+
 // sf_record_step / sf_record_flush (sf_record.hpp): one wavefront per arena and workgroup, lane g = commanded human g.
 // mode 0 the loop top, mode 1 between the halves, mode 2 behind the second half, mode 3 the flush.  Modes 0, 2 and 3 are
 // lane 0's alone.  Mode 1: one flag-word load, the ballot, the lane's rank in it, one byte store; the cursor by lane 0.
@@ -514,6 +529,30 @@ struct HipRT {
     if (io.d_counts || io.d_digest)
       if ((rc = launch(k_state_init, dim3((unsigned)((io.rows + 255) / 256)), dim3(256), 0, io))) return rc;
     return launch(k_state_records, dim3((unsigned)io.rows, (unsigned)k.parts), dim3(64), 0, k);
+  }
+  // sf_state_put_device: the row map, every part given and the two outputs checked as sf_state_device checks its own.
+  // bytes: what each of the eleven buffers must hold (Env::put_fill).  Nothing is launched here
+  int check_state_put(const StatePut &k, const int64_t *bytes) {
+    SF_HIP(hipSetDevice(device));
+    const sf_state_put_io &io = k.io;
+    const struct { const void *q; size_t align; const char *name; } bufs[11] = {
+        {io.d_row_of_arena, 4, "d_row_of_arena"}, {io.d_hdr, 8, "d_hdr"}, {io.d_humans, 4, "d_humans"}, {io.d_zombies, 4, "d_zombies"},
+        {io.d_bullets, 4, "d_bullets"}, {io.d_portals, 4, "d_portals"}, {io.d_cell_flags, 1, "d_cell_flags"}, {io.d_cell_dmg, 4, "d_cell_dmg"},
+        {io.d_cell_portal, 4, "d_cell_portal"}, {io.d_status, 4, "d_status"}, {io.d_selected, 1, "d_selected"}};
+    for (int j = 0; j < 11; ++j) {
+      if (!bufs[j].q || bytes[j] == 0) continue;  // (a table cut to 0 slots is never read)
+      if (int rc = check_device_range(bufs[j].q, (size_t)bytes[j], bufs[j].align, bufs[j].name, "sf_state_put_device")) return rc;
+    }
+    return SF_OK;
+  }
+  // the init, the check over the rows, the write over the arenas
+  int launch_state_put(const StatePut &k, const int64_t *) {
+    SF_HIP(hipSetDevice(device));
+    const int units = put_units(k).total();
+    int rc;
+    if ((rc = launch(k_put_init, dim3((unsigned)((k.io.rows + 255) / 256)), dim3(256), 0, k))) return rc;
+    if ((rc = launch(k_put_check, dim3((unsigned)k.io.rows, (unsigned)state_parts_for(units, k.io.rows)), dim3(64), 0, k))) return rc;
+    return launch(k_put_write, dim3((unsigned)k.A, (unsigned)state_parts_for(units, k.A)), dim3(64), 0, k);
   }
   // sf_record_step / sf_record_flush: one of the record launches (k_record's mode)
   int launch_record(const Record &k, int mode) {
@@ -1059,6 +1098,20 @@ int sf_dump_arena(sf_env *env, int32_t arena, sf_arena_hdr *hdr, sf_human_rec *h
 int sf_state_device(sf_env *env, const sf_state_io *io) {
   SF_ENV(env);
   return env->e.state_device(io);
+}
+int sf_state_put_device(sf_env *env, const sf_state_put_io *io) {
+  if (!env) return fail(SF_ERR_ARG, "sf_state_put_device: null env");
+  return env->e.state_put_device(io);
+}
+int sf_state_put_status(sf_env *env, int64_t out_host[4]) {
+  if (!env) return fail(SF_ERR_ARG, "sf_state_put_status: null env");
+  return env->e.state_put_status(out_host);
+}
+int sf_load_arena(sf_env *env, int32_t arena, const sf_arena_hdr *hdr, const sf_human_rec *humans, const sf_zombie_rec *zombies,
+                  const sf_bullet_rec *bullets, const sf_portal_rec *portals, const uint8_t *cell_flags, const int32_t *cell_dmg,
+                  const int32_t *cell_portal) {
+  if (!env) return fail(SF_ERR_ARG, "sf_load_arena: null env");
+  return env->e.load_arena(arena, hdr, humans, zombies, bullets, portals, cell_flags, cell_dmg, cell_portal);
 }
 int sf_state_bytes(sf_env *env, const sf_state_io *io, int64_t bytes_out[10]) {
   SF_ENV(env);

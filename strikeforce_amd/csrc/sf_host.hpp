@@ -23,6 +23,7 @@
 #include "sf_signals.hpp"
 #include "sf_record.hpp"
 #include "sf_state_records.hpp"
+#include "sf_state_put.hpp"
 
 namespace sf {
 
@@ -193,6 +194,13 @@ struct has_state_records : std::false_type {};
 template <class R>
 struct has_state_records<R, decltype((void)std::declval<R &>().launch_state_records(std::declval<const StateRec &>(), nullptr))>
     : std::true_type {};
+
+// whether a runtime has the state-put kernels (sf_state_put_device: k_put_init / k_put_check / k_put_write).  The HIP runtime has
+// them; the wave emulator's runtime of tests/emu does not, and sf_state_put_device / sf_load_arena answer SF_ERR_STATE there
+template <class R, class = void>
+struct has_state_put : std::false_type {};
+template <class R>
+struct has_state_put<R, decltype((void)std::declval<R &>().launch_state_put(std::declval<const StatePut &>(), nullptr))> : std::true_type {};
 
 // whether a runtime has the episode log's own kernels: k_step's LOG instance (chosen through ep_log_on) and k_ep_late (the
 // record behind k_reset and the split step's second half).  The HIP runtime has them; the wave emulator's runtime of
@@ -399,7 +407,7 @@ struct Env {
 
   void destroy() {
     void *ptrs[] = {d_logt, d_exptab, d_tab, d_map_flags, d_map_pidx, d_map_exits, p.hum, p.zom, p.bul, p.por, p.rng, p.rng2, p.scal, p.results,
-                    p.flags, p.aux_dmg, p.aux_pidx, d_tb, d_serial, d_cmd, d_obs, d_nzprev, d_perm, tab.ep_ring, d_ep_cursor,
+                    p.flags, p.aux_dmg, p.aux_pidx, d_tb, d_serial, d_cmd, d_obs, d_nzprev, d_perm, tab.ep_ring, d_ep_cursor, d_put_verdict, d_put_counters, d_put_status,
                     d_ep_plan, d_ep_out, d_ep_counts, (void *)rp.streams, (void *)rp.off, rp.status, rp.taken, d_amask};
     for (void *q : ptrs)
       if (q) rt.free(q);
@@ -1230,6 +1238,138 @@ struct Env {
       out[a] = digest_of(hdr, hs.data(), zs.data(), bs.data(), ps.data(), cf.data(), cd.data(), cp.data());
     }
     return SF_OK;
+  }
+
+  // ---- sf_state_put_device / sf_load_arena (the lane functions are sf_state_put.hpp's, k_put_*) ---------------------
+  // the rows' verdicts and extents and the call's counters: allocated by the first call that needs more rows than any
+  // call before it, as sf_rollout_gae's array is
+  int32_t *d_put_verdict = nullptr;
+  unsigned long long *d_put_counters = nullptr;
+  int32_t put_rows = 0;
+  // the kernels' struct and the bytes each of the eleven buffers must hold (the row map, the eight parts, the two outputs)
+  int put_fill(const sf_state_put_io *io, StatePut &k, int64_t bytes[11]) {
+    const std::string who = "sf_state_put_device";
+    if (!io) return fail(SF_ERR_ARG, who + ": null argument");
+    if (!was_reset) return fail(SF_ERR_STATE, who + " before sf_reset");
+    if (int rc = not_mid_step(who.c_str())) return rc;
+    if (rp.status) return fail(SF_ERR_STATE, who + " while a replay is loaded (sf_replay_load)");
+    if (!io->d_row_of_arena) return fail(SF_ERR_ARG, who + ": null d_row_of_arena");
+    if (io->rows < 1) return fail(SF_ERR_ARG, who + ": rows must be at least 1");
+    if (io->humans < 0 || io->humans > p.H || io->zombies < 0 || io->zombies > p.Z || io->bullets < 0 || io->bullets > p.B ||
+        io->portals < 0 || io->portals > p.P)
+      return fail(SF_ERR_ARG, who + ": humans / zombies / bullets / portals must be 0 .. the configuration's cap");
+    const int ncell = (io->d_cell_flags ? 1 : 0) + (io->d_cell_dmg ? 1 : 0) + (io->d_cell_portal ? 1 : 0);
+    if (ncell != 0 && ncell != 3) return fail(SF_ERR_ARG, who + ": d_cell_flags, d_cell_dmg and d_cell_portal must be given all or none");
+    if (!io->d_hdr && !io->d_humans && !io->d_zombies && !io->d_bullets && !io->d_portals && !ncell)
+      return fail(SF_ERR_ARG, who + ": every part is NULL");
+    memset(&k, 0, sizeof k);
+    k.hum = p.hum, k.zom = p.zom, k.bul = p.bul, k.por = p.por, k.rng = p.rng, k.rng2 = p.rng2, k.scal = p.scal, k.flags = p.flags;
+    k.aux_dmg = p.aux_dmg, k.aux_pidx = p.aux_pidx, k.map_pidx = p.map_pidx;
+    k.A = p.A, k.cells_pad = p.cells_pad;
+    k.c = PutCfg{p.F, p.N, p.M, p.H, p.Z, p.B, p.P, cells, p.mode, p.n_agents, p.ind, p.npc_block, p.auto_reset, p.reseed};
+    k.io = *io;
+    const int64_t R = io->rows, C = cells;
+    const int64_t b[11] = {(int64_t)p.A * 4, R * (int64_t)sizeof(sf_arena_hdr), R * io->humans * (int64_t)sizeof(sf_human_rec),
+                           R * io->zombies * (int64_t)sizeof(sf_zombie_rec), R * io->bullets * (int64_t)sizeof(sf_bullet_rec),
+                           R * io->portals * (int64_t)sizeof(sf_portal_rec), R * C, R * C * 4, R * C * 4, (int64_t)p.A * 4,
+                           (int64_t)p.A * p.n_agents};
+    memcpy(bytes, b, sizeof b);
+    return SF_OK;
+  }
+  // three stream-ordered launches; nothing is copied or waited for, and nothing allocated once the verdict rows suffice
+  int state_put_device(const sf_state_put_io *io) {
+    if constexpr (has_state_put<RT>::value) {
+      StatePut k;
+      int64_t bytes[11];
+      if (int rc = put_fill(io, k, bytes)) return rc;
+      if (int rc = rt.check_state_put(k, bytes)) return rc;
+      if (!d_put_counters) {
+        if (int rc = alloc(d_put_counters, (size_t)PUT_COUNTERS)) return rc;
+        rt.zero(d_put_counters, PUT_COUNTERS * sizeof(unsigned long long));
+      }
+      if (io->rows > put_rows) {
+        if (d_put_verdict) {
+          if (int rc = rt.sync()) return rc;  // an earlier call's launches may still read the rows
+          rt.free(d_put_verdict);
+          d_put_verdict = nullptr, put_rows = 0;
+        }
+        if (int rc = alloc(d_put_verdict, (size_t)io->rows * PUT_ROW_WORDS)) return rc;
+        put_rows = io->rows;
+      }
+      k.verdict = d_put_verdict, k.counters = d_put_counters;
+      if (int rc = rt.launch_state_put(k, bytes)) return rc;
+      steps_since_rank = 1 << 30;  // the populations the launch order was built from are gone
+      return SF_OK;
+    } else {
+      (void)io;
+      return fail(SF_ERR_STATE, "sf_state_put_device: this runtime has no state-put kernels");
+    }
+  }
+  int state_put_status(int64_t out[4]) {
+    if (!out) return fail(SF_ERR_ARG, "sf_state_put_status: null argument");
+    for (int j = 0; j < 4; ++j) out[j] = 0;
+    if (!d_put_counters) return rt.sync();
+    unsigned long long c[PUT_COUNTERS];
+    rt.d2h(c, d_put_counters, sizeof c);
+    rt.zero(d_put_counters, sizeof c);
+    if (int rc = rt.sync()) return rc;
+    for (int j = 0; j < 4; ++j) out[j] = (int64_t)c[j];
+    return SF_OK;
+  }
+  // the host mirror of sf_dump_arena: one row of whole pools through staging memory of the call's own, then the device path
+  int load_arena(int a, const sf_arena_hdr *hdr, const sf_human_rec *hs, const sf_zombie_rec *zs, const sf_bullet_rec *bs,
+                 const sf_portal_rec *ps, const uint8_t *cf, const int32_t *cd, const int32_t *cp) {
+    if constexpr (has_state_put<RT>::value) {
+      if (a < 0 || a >= p.A) return fail(SF_ERR_ARG, "sf_load_arena: arena out of range");
+      const size_t C = (size_t)cells;
+      const struct { const void *src; size_t bytes; } part[8] = {
+          {hdr, sizeof(sf_arena_hdr)}, {hs, p.H * sizeof(sf_human_rec)}, {zs, p.Z * sizeof(sf_zombie_rec)}, {bs, p.B * sizeof(sf_bullet_rec)},
+          {ps, p.P * sizeof(sf_portal_rec)}, {cf, C}, {cd, C * 4}, {cp, C * 4}};
+      size_t off[8], at = ((size_t)p.A * 4 + 255u) & ~(size_t)255u;  // the row map first
+      for (int j = 0; j < 8; ++j) off[j] = at, at = (at + (part[j].src ? part[j].bytes : 0) + 255u) & ~(size_t)255u;
+      uint8_t *stage = nullptr;
+      if (int rc = alloc(stage, at)) return rc;
+      std::vector<int32_t> map((size_t)p.A, -1);
+      map[(size_t)a] = 0;
+      rt.h2d(stage, map.data(), map.size() * 4);
+      for (int j = 0; j < 8; ++j)
+        if (part[j].src) rt.h2d(stage + off[j], part[j].src, part[j].bytes);
+      auto at_or_null = [&](int j) -> const void * { return part[j].src ? stage + off[j] : nullptr; };
+      sf_state_put_io io;
+      memset(&io, 0, sizeof io);
+      io.d_row_of_arena = reinterpret_cast<const int32_t *>(stage), io.rows = 1;
+      io.humans = p.H, io.zombies = p.Z, io.bullets = p.B, io.portals = p.P;
+      io.d_hdr = static_cast<const sf_arena_hdr *>(at_or_null(0)), io.d_humans = static_cast<const sf_human_rec *>(at_or_null(1));
+      io.d_zombies = static_cast<const sf_zombie_rec *>(at_or_null(2)), io.d_bullets = static_cast<const sf_bullet_rec *>(at_or_null(3));
+      io.d_portals = static_cast<const sf_portal_rec *>(at_or_null(4)), io.d_cell_flags = static_cast<const uint8_t *>(at_or_null(5));
+      io.d_cell_dmg = static_cast<const int32_t *>(at_or_null(6)), io.d_cell_portal = static_cast<const int32_t *>(at_or_null(7));
+      int rc = rt.sync();
+      int32_t status = 0;
+      if (!rc) rc = state_put_one(io, a, &status);
+      rt.free(stage);
+      if (rc) return rc;
+      if (status != 0) {
+        static const char *names[] = {"the header", "a human", "a zombie", "a bullet", "an exit", "a cell"};
+        std::string why;
+        for (int j = 0; j < 6; ++j)
+          if (status & (1 << j)) why += std::string(why.empty() ? "" : ", ") + names[j];
+        return fail(SF_ERR_ARG, "sf_load_arena: refused, a field out of range in " + why);
+      }
+      return SF_OK;
+    } else {
+      (void)a, (void)hdr, (void)hs, (void)zs, (void)bs, (void)ps, (void)cf, (void)cd, (void)cp;
+      return fail(SF_ERR_STATE, "sf_load_arena: this runtime has no state-put kernels");
+    }
+  }
+  // sf_load_arena's launch, with a status array of the library's own of which arena a's word is read back
+  int32_t *d_put_status = nullptr;
+  int state_put_one(sf_state_put_io &io, int a, int32_t *status) {
+    if (!d_put_status)
+      if (int rc = alloc(d_put_status, (size_t)p.A)) return rc;
+    io.d_status = d_put_status;
+    if (int rc = state_put_device(&io)) return rc;
+    rt.d2h(status, d_put_status + a, 4);
+    return rt.sync();
   }
 
   // sf_state_device / sf_state_bytes: the kernel's struct and the bytes each of the ten outputs must hold

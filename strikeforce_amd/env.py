@@ -78,6 +78,8 @@ def load_library():
             abi.bind_signals(L, "sf_")
         if hasattr(L, "sf_state_device"):  # (state records on the device; an older build loaded through SF_LIBRARY_PATH lacks them)
             abi.bind_state(L, "sf_")
+        if hasattr(L, "sf_state_put_device"):  # (arenas written from records; an older build loaded through SF_LIBRARY_PATH lacks it)
+            abi.bind_state_put(L, "sf_")
         if hasattr(L, "sf_record_create"):  # (recording of games; an older build loaded through SF_LIBRARY_PATH lacks it)
             abi.bind_record(L, "sf_")
         if hasattr(L, "sf_action_mask_device"):  # (action masks; an older build loaded through SF_LIBRARY_PATH lacks them)
@@ -120,7 +122,7 @@ EXPORTS = ["sf_create", "sf_destroy", "sf_config_defaults", "sf_reset", "sf_step
            "sf_episode_log", "sf_episodes", "sf_episodes_device", "sf_episode_ring", "sf_episodes_allgather",
            "sf_replay_load", "sf_replay_step", "sf_replay_status", "sf_replay_status_device", "sf_replay_commands_device",
            "sf_reset_arenas"] + ["sf_" + n for n in abi.SNAPSHOT_EXPORTS + abi.SIGNALS_EXPORTS + abi.STATE_EXPORTS +
-                                     abi.RECORD_EXPORTS + abi.ACTION_MASK_EXPORTS]
+                                     abi.RECORD_EXPORTS + abi.ACTION_MASK_EXPORTS + abi.STATE_PUT_EXPORTS]
 
 EPISODE_HDR_WORDS = 8  # SF_EPISODE_HDR_WORDS
 
@@ -285,6 +287,47 @@ def decode_state(hdr=None, humans=None, zombies=None, bullets=None, portals=None
     if counts is not None:
         assert counts.shape[-1] == abi.STATE_COUNT_WORDS
         out["counts"] = {n: counts[..., j] for j, n in enumerate(abi.STATE_COUNT_FIELDS)}
+    return out
+
+
+def encode_state(hdr=None, humans=None, zombies=None, bullets=None, portals=None):
+    """The inverse of decode_state(): field dictionaries -> record arrays.  Each table {field: [...]} (cons / throw_cnt with a
+    last axis of 4) -> int32 [..., words of its record]; hdr {the ten 64-bit fields, rng [rows][18], done, outcome} -> int32
+    [rows][40].  Numpy arrays give numpy arrays, torch tensors give torch tensors on the fields' device.  -> {name: array}
+    for the parts given, what ArenaBatch.put_state takes as its raw records."""
+    out = {}
+
+    def new(shape, proto):
+        if isinstance(proto, np.ndarray) or not hasattr(proto, "device"):
+            return np.zeros(shape, dtype=np.int32)
+        import torch
+        return torch.zeros(shape, dtype=torch.int32, device=proto.device)
+
+    for name, d, struct in (("humans", humans, abi.HumanRec), ("zombies", zombies, abi.ZombieRec),
+                            ("bullets", bullets, abi.BulletRec), ("portals", portals, abi.PortalRec)):
+        if d is None:
+            continue
+        fields = abi.record_fields(struct)
+        first = d[fields[0][0]]
+        first = first if hasattr(first, "shape") else np.asarray(first)
+        t = new(tuple(first.shape) + (C.sizeof(struct) // 4,), first)
+        for n, w, k in fields:
+            v = d[n] if hasattr(d[n], "shape") else np.asarray(d[n])
+            if k == 1:
+                t[..., w] = v
+            else:
+                t[..., w:w + k] = v
+        out[name] = t
+    if hdr is not None:
+        names = [n for n, _ in abi.ArenaHdr._fields_[:10]]
+        first = hdr[names[0]] if hasattr(hdr[names[0]], "shape") else np.asarray(hdr[names[0]])
+        t = new(tuple(first.shape) + (C.sizeof(abi.ArenaHdr) // 4,), first)
+        i64 = t[..., :20].view(np.int64 if isinstance(t, np.ndarray) else __import__("torch").int64)
+        for j, n in enumerate(names):
+            i64[..., j] = hdr[n] if hasattr(hdr[n], "shape") else np.asarray(hdr[n])
+        t[..., 20:38] = hdr["rng"] if hasattr(hdr["rng"], "shape") else np.asarray(hdr["rng"])
+        t[..., 38], t[..., 39] = hdr["done"], hdr["outcome"]
+        out["hdr"] = t
     return out
 
 
@@ -587,6 +630,119 @@ class ArenaBatch:
         """sf_state_digest's values computed on the device, in stream order: an int64 tensor [arenas] holding the bits of
         the unsigned digests (`.cpu().numpy().view(numpy.uint64)` equals digest()).  The same tensor is rewritten by every call."""
         return self.state_records(humans=0, zombies=0, bullets=0, portals=0, hdr=False, counts=False, digest=True)["raw"]["digest"]
+
+    def state_put_device(self, io):
+        """sf_state_put_device with a ready abi.StatePutIO: three stream-ordered launches, nothing else."""
+        if not hasattr(self.L, "sf_state_put_device"):
+            raise StrikeForceError("this build of libstrikeforce_amd.so has no sf_state_put_device")
+        self._ck(self.L.sf_state_put_device(self.h, C.byref(io)), "sf_state_put_device")
+
+    def state_put_io(self, records, row_of_arena=None, status=True, selected=False):
+        """The request of put_state() without the launch: (abi.StatePutIO, the tensors it points at).  records: what
+        state_records() returned or its "raw" dict — torch tensors on the device under any of hdr [rows][40], humans
+        [rows][n][28], zombies [rows][n][7], bullets [rows][n][11], portals [rows][n][4] (int32; n = the table's cut) and
+        cell_flags (uint8) / cell_dmg / cell_portal (int32) [rows][cells], all three or none.  row_of_arena: device int32
+        [arenas], None = arena a takes row a (rows == arenas)."""
+        import torch
+        cfg = self.cfg
+        dev = "cuda:%d" % cfg.device
+        raw = dict(records.get("raw", records))
+        keep = {}
+        io = abi.StatePutIO()
+        rows = None
+        for name, words in (("hdr", 40), ("humans", 28), ("zombies", 7), ("bullets", 11), ("portals", 4),
+                            ("cell_flags", None), ("cell_dmg", None), ("cell_portal", None)):
+            t = raw.get(name)
+            if t is None:
+                continue
+            want = torch.uint8 if name == "cell_flags" else torch.int32
+            if t.dtype != want or not t.is_cuda or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s tensor on the device" % (name, want))
+            if words is not None and t.shape[-1] != words:
+                raise ValueError("%s must have %d words per record" % (name, words))
+            if rows is not None and t.shape[0] != rows:
+                raise ValueError("every part must have the same number of rows")
+            rows = int(t.shape[0])
+            if name in ("humans", "zombies", "bullets", "portals"):
+                setattr(io, name, int(t.shape[1]))
+            keep[name] = t
+            ptr = t.data_ptr()
+            if t.numel() == 0:  # a table of 0 slots is still given (its whole pool becomes empty): any valid address
+                if getattr(self, "_put_nothing", None) is None:
+                    self._put_nothing = torch.zeros(4, dtype=torch.int32, device=dev)
+                ptr = self._put_nothing.data_ptr()
+            setattr(io, "d_" + name, ptr)
+        if rows is None:
+            raise ValueError("no part given")
+        if row_of_arena is None:
+            if rows != cfg.arenas:
+                raise ValueError("without row_of_arena the parts must have one row per arena")
+            own = self.__dict__.setdefault("_put_identity", None)
+            if own is None:
+                own = self._put_identity = torch.arange(cfg.arenas, dtype=torch.int32, device=dev)
+            row_of_arena = own
+        elif not hasattr(row_of_arena, "data_ptr"):
+            row_of_arena = torch.from_numpy(np.ascontiguousarray(row_of_arena, dtype=np.int32).reshape(-1)).to(dev)
+        if row_of_arena.dtype != torch.int32 or not row_of_arena.is_cuda or row_of_arena.numel() != cfg.arenas:
+            raise ValueError("row_of_arena must be an int32 tensor [arenas] on the device")
+        keep["row_of_arena"] = row_of_arena
+        io.d_row_of_arena, io.rows = row_of_arena.data_ptr(), rows
+        own = self.__dict__.setdefault("_put_outputs", {})
+        if status:
+            if "status" not in own:
+                own["status"] = torch.zeros((cfg.arenas,), dtype=torch.int32, device=dev)
+            keep["status"], io.d_status = own["status"], own["status"].data_ptr()
+        if selected:
+            if "selected" not in own:
+                own["selected"] = torch.zeros((cfg.arenas, cfg.n_agents), dtype=torch.uint8, device=dev)
+            keep["selected"], io.d_selected = own["selected"], own["selected"].data_ptr()
+        return io, keep
+
+    def put_state(self, records, row_of_arena=None, selected=False):
+        """Write arenas from canonical records on the device (sf_state_put_device), the inverse of state_records(): arena a
+        takes row row_of_arena[a] of the given parts (-1: untouched; None: row a).  -> the status tensor, int32 [arenas]:
+        -1 not named, 0 written, > 0 refused (abi.PUT_BAD_* bits); with selected=True a pair with the uint8
+        [arenas][n_agents] mask of the agents whose arena was written (what Signals.step's rebase_ptr, the policy's
+        reset_memory and the rollout buffer take).  Both tensors are the batch's own and rewritten by every call; nothing
+        is read on the host."""
+        io, keep = self.state_put_io(records, row_of_arena, True, selected)
+        self._put_last = keep  # (alive while the launches may still be queued)
+        self.state_put_device(io)
+        return (keep["status"], keep["selected"]) if selected else keep["status"]
+
+    def put_status(self):
+        """Arenas written, refused and naming a row out of range since the last call (sf_state_put_status); synchronises."""
+        out = (C.c_int64 * 4)()
+        self._ck(self.L.sf_state_put_status(self.h, C.byref(out)), "sf_state_put_status")
+        return dict(zip(abi.STATE_PUT_STATUS_FIELDS, (int(x) for x in out)))
+
+    def load_arena(self, arena, hdr=None, humans=None, zombies=None, bullets=None, portals=None, cell_flags=None,
+                   cell_dmg=None, cell_portal=None):
+        """The host mirror of dump_raw(): one arena from whole pools in host memory (sf_load_arena), any part None.  hdr: an
+        abi.ArenaHdr; the tables: ctypes arrays of the records or int32 numpy arrays [cap][words]; the cell tables: numpy
+        uint8 / int32 [cells].  Synchronises; a refused state raises with the reason."""
+        caps = {"humans": (self.cfg.cap_humans, 28), "zombies": (self.cfg.cap_zombies, 7), "bullets": (self.cfg.cap_bullets, 11),
+                "portals": (self.cfg.cap_portals, 4)}
+        cells = self.cfg.floors * self.cfg.rows * self.cfg.cols
+        hold, args = [], []
+        for name, x in (("hdr", hdr), ("humans", humans), ("zombies", zombies), ("bullets", bullets), ("portals", portals),
+                        ("cell_flags", cell_flags), ("cell_dmg", cell_dmg), ("cell_portal", cell_portal)):
+            if x is None:
+                args.append(None)
+                continue
+            if isinstance(x, np.ndarray) or name.startswith("cell"):
+                x = np.ascontiguousarray(x, dtype=np.uint8 if name == "cell_flags" else np.int32)
+                n = 40 if name == "hdr" else cells if name.startswith("cell") else caps[name][0] * caps[name][1]
+                if x.size != n:
+                    raise ValueError("%s must hold the whole pool (%d values)" % (name, n))
+                hold.append(x)
+                args.append(x.ctypes.data)
+            else:
+                if name in caps and len(x) != caps[name][0]:
+                    raise ValueError("%s must hold the whole pool (%d records)" % (name, caps[name][0]))
+                hold.append(x)
+                args.append(C.addressof(x))
+        self._ck(self.L.sf_load_arena(self.h, int(arena), *args), "sf_load_arena")
 
     def snapshot_slot_bytes(self):
         """(device bytes, blob bytes) one snapshot slot of this configuration takes: to budget before snapshot()."""
