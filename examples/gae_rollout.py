@@ -92,7 +92,8 @@ for t in range(steps):
     if t and t % T == 0:  # the hand-over: every agent's buffer is full, this tick is the one behind slot T - 1
         rb.gae(GAMMA, LAMBDA, next_value=d_value, next_mask=d_selected, out=out)
         rb.ready_mask(d_ready)
-        # ... a learner's epochs over rb.state(t), rb.action, rb.logp, rb.first, the returns and the advantages go here ...
+        # ... a learner's epochs over rb.state(t), rb.action, rb.logp, rb.first, the returns and the advantages go here
+        # (examples/dense_epoch.py: the states as dense rows for a torch module, rb.dense(t)) ...
         adv_sum += out[2].sum(dtype=torch.float64)
         per_game_yield()
         rb.release()

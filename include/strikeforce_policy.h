@@ -426,6 +426,43 @@ typedef struct sf_rollout_gae_io {
 } sf_rollout_gae_io;
 int sf_rollout_gae(sf_rollout *r, const sf_rollout_gae_io *io);
 
+/* ---- the rollout buffer's states as dense rows: what a learner's own network reads --------------------------------------
+ * The reference's epochs run model->forward(states[i]) with gradients on the dense 32 x 31 x 31 observation
+ * (Agent.hpp:392, RewardNet.hpp:265-274); the buffer keeps states[i] as the observation's list.  This call expands stored
+ * lists into dense rows of the caller's, in the element type and layout the caller's module wants.  One launch on the
+ * rollout's stream, no synchronisation.
+ *
+ * Row b is the cell d_cells[b] = t * agents + agent (any order, repeats allowed), or with d_cells NULL the cell
+ * (slot, agent0 + b).  Every one of a row's 30 752 elements is written:
+ *   a good cell — inside [0, T * agents), stored count <= list_cap: for each entry e < count the element at the position
+ *     the key k names holds vals[e]; NCHW position ((k & 511) / 9 * 31 + (k >> 9 & 31)) * 31 + (k >> 14 & 31), NHWC the
+ *     same three numbers as ((k >> 9 & 31) * 31 + (k >> 14 & 31)) * 32 + (k & 511) / 9; every other element is +0;
+ *     d_valid[b] = 1.  Lists need not be sorted; of two entries that name one position either value stays.  An entry whose
+ *     key names no position (channel above 31, row or column above 30; the simulator writes none) is skipped.
+ *   a bad cell — its list did not fit (count > list_cap, the 0xffffffff marker included) or the cell lies outside the
+ *     buffer: the whole row is +0 and d_valid[b] = 0.  Nothing is read through an out-of-range cell.
+ * SF_DENSE_F32 keeps the value's bits (-0, infinities, NaN payloads); SF_DENSE_BF16 and SF_DENSE_F16 round the f32 value
+ * to nearest even (F16 overflows to infinity and keeps subnormals; a NaN stays a NaN, payload unspecified).
+ * `fill` is not looked at: a slot behind an agent's cursor expands to whatever is stored there.
+ * SF_ERR_STATE: states are not kept.  SF_ERR_ARG: rows outside [1, SF_ROLLOUT_DENSE_ROWS_MAX] (the cap keeps every
+ * destination offset below 2^31 bytes); with d_cells NULL, slot outside [0, T), agent0 < 0 or agent0 + rows > agents;
+ * an unknown dtype or layout; d_dense NULL or not 16-byte aligned. */
+#define SF_DENSE_F32 0
+#define SF_DENSE_BF16 1
+#define SF_DENSE_F16 2
+#define SF_DENSE_NCHW 0   /* [rows][32][31][31], sf_observe_device's own order */
+#define SF_DENSE_NHWC 1   /* [rows][31][31][32], channel fastest */
+#define SF_ROLLOUT_DENSE_ROWS_MAX 16384
+typedef struct sf_rollout_dense_io {
+  const int32_t *d_cells;  /* device, [rows]: cell = t * agents + agent; NULL: cells (slot, agent0 + b) */
+  int32_t slot, agent0;    /* looked at only when d_cells is NULL */
+  int32_t rows;
+  int32_t dtype, layout;
+  void *d_dense;           /* device, [rows][30752] elements of dtype, contiguous, 16-byte aligned */
+  uint8_t *d_valid;        /* device, [rows], may be NULL */
+} sf_rollout_dense_io;
+int sf_rollout_dense(sf_rollout *r, const sf_rollout_dense_io *io);
+
 /* ---- parameters in: what a learner hands back ---------------------------------------------------------------------------
  * The parameters the next forward sees are these (optimizer->step(), bots/bot-1/Agent.hpp:415-417, then model->forward,
  * :202; RewardNet::train_epoch does the same to the discriminator, :428): d_w holds DEVICE pointers, same fields / shapes /

@@ -43,6 +43,7 @@
 #include "sf_policy_mask.hpp"
 #include "sf_rollout.hpp"
 #include "sf_rollout_gae.hpp"
+#include "sf_rollout_dense.hpp"
 
 namespace sfp {
 
@@ -957,6 +958,44 @@ int sf_rollout_gae(sf_rollout *rr, const sf_rollout_gae_io *io) {
     hipLaunchKernelGGL(sfp::k_rollout_gae, dim3((unsigned)((r->agents + 63) / 64)), dim3(64), 0, r->stream, d, g);
     SFP_HIP(hipGetLastError());
   }
+  return SF_OK;
+}
+
+int sf_rollout_dense(sf_rollout *rr, const sf_rollout_dense_io *io) {
+  Rollout *r = reinterpret_cast<Rollout *>(rr);
+  if (!io) return sfp::fail(SF_ERR_ARG, "null io");
+  // what the struct alone decides, then the object
+  if (io->rows < 1 || io->rows > SF_ROLLOUT_DENSE_ROWS_MAX) return sfp::fail(SF_ERR_ARG, "sf_rollout_dense: rows must be 1..SF_ROLLOUT_DENSE_ROWS_MAX");
+  if (io->dtype != SF_DENSE_F32 && io->dtype != SF_DENSE_BF16 && io->dtype != SF_DENSE_F16)
+    return sfp::fail(SF_ERR_ARG, "sf_rollout_dense: unknown dtype");
+  if (io->layout != SF_DENSE_NCHW && io->layout != SF_DENSE_NHWC) return sfp::fail(SF_ERR_ARG, "sf_rollout_dense: unknown layout");
+  if (!io->d_dense || !sfp::aligned16(io->d_dense)) return sfp::fail(SF_ERR_ARG, "sf_rollout_dense: d_dense must be set and 16-byte aligned");
+  if (!r) return sfp::fail(SF_ERR_ARG, "null rollout");
+  const sfp::RolloutDst &d = r->d;
+  if (!d.keys) return sfp::fail(SF_ERR_STATE, "sf_rollout_dense: this rollout keeps no states (keys == NULL at sf_rollout_create)");
+  if (!io->d_cells && (io->slot < 0 || io->slot >= d.T || io->agent0 < 0 || io->rows > r->agents - io->agent0))
+    return sfp::fail(SF_ERR_ARG, "sf_rollout_dense: slot or agents out of range for this rollout");
+  sfp::DenseArgs g{};
+  g.keys = d.keys, g.vals = reinterpret_cast<const uint32_t *>(d.vals), g.counts = d.counts, g.cells = io->d_cells;
+  const uint64_t n_cells = (uint64_t)d.T * (uint64_t)d.stride;  // (a cell is an int32: none reaches 2^31)
+  g.n_cells = (uint32_t)(n_cells < 0x80000000ull ? n_cells : 0x80000000ull);
+  // (slot * agents + agent0 is below n_cells; where that is capped no int32 holds it and d_cells is the way in)
+  if (!io->d_cells) {
+    const uint64_t c0 = (uint64_t)io->slot * (uint64_t)d.stride + (uint64_t)io->agent0;
+    if (c0 + (uint64_t)io->rows > 0x80000000ull) return sfp::fail(SF_ERR_ARG, "sf_rollout_dense: the slot's cells do not fit an int32");
+    g.cell0 = (int32_t)c0;
+  }
+  g.list_cap = d.list_cap, g.dense = io->d_dense, g.valid = io->d_valid;
+  SFP_HIP(hipSetDevice(r->device));
+  const dim3 grid((unsigned)io->rows), block(sfp::DENSE_WG);
+  g.nhwc = io->layout == SF_DENSE_NHWC ? 1 : 0;
+  if (io->dtype == SF_DENSE_F32)
+    hipLaunchKernelGGL(sfp::k_rollout_dense<0>, grid, block, 0, r->stream, g);
+  else if (io->dtype == SF_DENSE_BF16)
+    hipLaunchKernelGGL(sfp::k_rollout_dense<1>, grid, block, 0, r->stream, g);
+  else
+    hipLaunchKernelGGL(sfp::k_rollout_dense<2>, grid, block, 0, r->stream, g);
+  SFP_HIP(hipGetLastError());
   return SF_OK;
 }
 

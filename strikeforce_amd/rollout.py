@@ -21,7 +21,13 @@ HIDDEN, ACTIONS = policy.HIDDEN, policy.ACTIONS
 # every sf_rollout_* symbol include/strikeforce_policy.h declares (sf_policy_update_actions is in policy.EXPORTS)
 EXPORTS = ["sf_rollout_create", "sf_rollout_destroy", "sf_rollout_set_stream", "sf_rollout_synchronize", "sf_rollout_record",
            "sf_rollout_fill_device", "sf_rollout_ready_device", "sf_rollout_status", "sf_rollout_returns", "sf_rollout_release",
-           "sf_rollout_state", "sf_rollout_continue", "sf_rollout_gae"]
+           "sf_rollout_state", "sf_rollout_continue", "sf_rollout_gae", "sf_rollout_dense"]
+
+# sf_rollout_dense: element types, layouts, the row cap and a row's elements (include/strikeforce_policy.h)
+DENSE_F32, DENSE_BF16, DENSE_F16 = 0, 1, 2
+DENSE_NCHW, DENSE_NHWC = 0, 1
+DENSE_ROWS_MAX = 16384
+DENSE_ROW = 32 * 31 * 31
 
 
 class Buffers(C.Structure):
@@ -45,6 +51,12 @@ class GaeIO(C.Structure):
                 ("next_group", C.c_int32), ("d_returns", C.c_void_p), ("d_v", C.c_void_p), ("d_adv", C.c_void_p)]
 
 
+class DenseIO(C.Structure):
+    """sf_rollout_dense_io."""
+    _fields_ = [("d_cells", C.c_void_p), ("slot", C.c_int32), ("agent0", C.c_int32), ("rows", C.c_int32), ("dtype", C.c_int32),
+                ("layout", C.c_int32), ("d_dense", C.c_void_p), ("d_valid", C.c_void_p)]
+
+
 def _bind(L):
     if getattr(L, "_sf_rollout_bound", False):
         return
@@ -64,6 +76,8 @@ def _bind(L):
     if hasattr(L, "sf_rollout_gae"):  # (an older build loaded through SF_LIBRARY_PATH lacks them)
         L.sf_rollout_continue.argtypes = [vp, vp]
         L.sf_rollout_gae.argtypes = [vp, C.POINTER(GaeIO)]
+    if hasattr(L, "sf_rollout_dense"):
+        L.sf_rollout_dense.argtypes = [vp, C.POINTER(DenseIO)]
     for n in EXPORTS:
         if n != "sf_rollout_destroy" and hasattr(L, n):
             getattr(L, n).restype = C.c_int
@@ -203,6 +217,58 @@ class RolloutBatch:
         io.d_returns, io.d_v, io.d_adv = (ptr(x) for x in out)
         self._ck(self.L.sf_rollout_gae(self.h, C.byref(io)), "sf_rollout_gae")
         return out
+
+    def dense(self, t=None, cells=None, agent0=0, rows=None, dtype=None, channels_last=False, out=None, valid=None):
+        """Stored observation lists as the dense rows a torch module reads (sf_rollout_dense): (dense, valid).  Rows: the
+        cells in `cells` (an int32 device tensor of t * agents + agent, any order), or agents agent0 .. agent0 + rows - 1 of
+        slot t (rows None: all behind agent0).  dense: [rows, 32, 31, 31] of dtype (torch.float32, the default, bfloat16 or
+        float16); with channels_last the memory is [rows, 31, 31, 32] and the tensor returned is its NCHW view, torch's
+        channels_last format.  valid: uint8 per row, 0 where the stored list did not fit (or the cell is outside the buffer)
+        and the row is all zero.  out / valid: tensors to write into (out: contiguous in the layout asked for, 16-byte
+        aligned, at least rows * 30752 elements).  At most DENSE_ROWS_MAX rows per call: walk a larger batch in chunks.
+        One launch on this object's stream."""
+        tc = self._torch
+        if not hasattr(self.L, "sf_rollout_dense"):
+            raise env.StrikeForceError("this build of libstrikeforce_amd.so has no sf_rollout_dense")
+        dtype = tc.float32 if dtype is None else dtype
+        codes = {tc.float32: DENSE_F32, tc.bfloat16: DENSE_BF16, tc.float16: DENSE_F16}
+        if dtype not in codes:
+            raise ValueError("dense: dtype must be torch.float32, torch.bfloat16 or torch.float16")
+        if (cells is None) == (t is None):
+            raise ValueError("dense: give a slot t or a tensor of cells, not both")
+        if cells is not None:
+            if cells.dtype != tc.int32 or not cells.is_cuda or not cells.is_contiguous():
+                raise ValueError("dense: cells must be a contiguous int32 device tensor")
+            rows = cells.numel() if rows is None else int(rows)
+            if rows > cells.numel():
+                raise ValueError("dense: more rows than cells")
+        elif rows is None:
+            rows = self.agents - int(agent0)
+        rows = int(rows)
+        if rows > DENSE_ROWS_MAX:
+            raise ValueError("dense: %d rows, at most %d per call (walk them in chunks)" % (rows, DENSE_ROWS_MAX))
+        if out is None and rows >= 1:
+            shape = (rows, 31, 31, 32) if channels_last else (rows, 32, 31, 31)
+            out = tc.empty(shape, dtype=dtype, device=self._dev)
+        if out is not None:
+            if out.dtype != dtype or out.numel() < rows * DENSE_ROW:
+                raise ValueError("dense: out must hold rows * 30752 elements of the dtype asked for")
+            if not (out.permute(0, 2, 3, 1) if channels_last and out.dim() == 4 and out.shape[1] == 32 else out).is_contiguous():
+                raise ValueError("dense: out is not contiguous in the layout asked for")
+        if valid is None and rows >= 1:
+            valid = tc.empty(rows, dtype=tc.uint8, device=self._dev)
+        elif valid is not None and (valid.dtype != tc.uint8 or valid.numel() < rows or not valid.is_contiguous()):
+            raise ValueError("dense: valid must be a contiguous uint8 tensor of at least `rows` elements")
+        io = DenseIO()
+        io.d_cells = None if cells is None else cells.data_ptr()
+        io.slot, io.agent0, io.rows = (0 if t is None else int(t)), int(agent0), rows
+        io.dtype, io.layout = codes[dtype], DENSE_NHWC if channels_last else DENSE_NCHW
+        io.d_dense = None if out is None else out.data_ptr()
+        io.d_valid = None if valid is None else valid.data_ptr()
+        self._ck(self.L.sf_rollout_dense(self.h, C.byref(io)), "sf_rollout_dense")
+        if channels_last and out.dim() == 4 and out.shape[-1] == 32 and out.shape[1] != 32:
+            out = out.permute(0, 3, 1, 2)  # the NCHW view of [rows, 31, 31, 32]
+        return out, valid
 
     def release(self, mask=None):
         """clear(): every ready agent starts at slot 0 again; with a mask (device uint8 per agent, or its address), the agents
